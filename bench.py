@@ -5,7 +5,9 @@ N = 1 (the driver's bench line): workload = BASELINE.json configs[1]: synthetic 
 12-of-19 seed with one transition, --nogapped (the HSP kernel path), both strands.  A step = one complete pass of the
 hot path over the batch, inputs already resident in HBM: position-table build from the resident target (B1), then
 seed-hit search + X-drop extension of the + strand and of the - strand of the query (B2), HSPs delivered to the host in
-the reference's order.  After the timed steps the same process adds, outside `value`:
+the reference's order.  A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs DIR (the HSP lists of the
+last timed step, one .npy per strand and field, float64), the line.  Its `roofline` is the dominant kernel's algorithmic bytes /
+HIP-event time of the timed steps, `traffic` a replay of the committed PMC table.  With --full the same process adds, outside `value`:
   roofline  k_scan_hits: algorithmic bytes / HIP-event time; `traffic` from THIS run's own rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE,
             one pass each over a child process that runs one step), calibrated with the factors tools/fetch_calib.sh measured on known
             byte counts (profiles/fetch_size_calibration.json); --no-pmc replays the committed table instead and says so
@@ -35,9 +37,10 @@ gathered and merged on rank 0 in the reference's order.  A step = the whole job.
 on the device of its LOCAL_RANK and that device 0 was left alone by the others (device_selfcheck).  At configs[3]'s own sizes unit 0 is
 the north-star query and its HSP list is checked against the reference's fingerprint inside the line (north_star_unit).
 (--q-unit-len / --q-units / --tlen-multi scale it for smoke runs; --bucket-owners splits every unit's search over the ranks by
-hashed-diagonal ownership; --force-multi runs this code path on one rank: the N = 1 point of the curve.)
+hashed-diagonal ownership; --force-multi runs this code path on one rank: the N = 1 point of the curve; its cpu_baseline needs --full;
+--dump-outputs writes every unit's merged HSP list on rank 0.)
 
-One JSON line on rank 0 (driver contract); extra objects: roofline, cpu_baseline, gapped, chain, parity, cli, north_star, content.
+One JSON line on rank 0 (driver contract); extra objects with --full: cpu_baseline, gapped, chain, parity, cli, north_star, content.
 """
 import argparse
 import collections
@@ -418,6 +421,25 @@ def hsp_rows_sha(hsps_by_strand):
     return h.hexdigest(), n
 
 
+DUMP_BUDGET_BYTES = 60_000_000          # --dump-outputs: the arrays' bytes in all (the .npy headers stay well inside 64 MB with them)
+HSP_FIELDS = ("pos1", "pos2", "length", "score")
+
+
+def dump_hsps(dirname, lists):
+    """--dump-outputs: HSP lists as a caller of the timed path receives them, [(name, array of lzgpu.HSP_DTYPE)] ->
+    DIR/<name>_<field>.npy (float64: exact for the 32-bit fields) and DIR/<name>_rows.npy (the list's full length).  A list longer
+    than its share of the budget is written as a fixed, seeded sample of its rows, in list order."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = (DUMP_BUDGET_BYTES // max(len(lists), 1) - 8) // (8 * len(HSP_FIELDS))
+    for name, hs in lists:
+        rows = hs
+        if len(hs) > cap:
+            rows = hs[np.sort(np.random.default_rng(1000).choice(len(hs), cap, replace=False))]
+        np.save(os.path.join(dirname, name + "_rows.npy"), np.array([len(hs)], dtype=np.float64))
+        for f in HSP_FIELDS:
+            np.save(os.path.join(dirname, "%s_%s.npy" % (name, f)), rows[f].astype(np.float64))
+
+
 def lav_fingerprint(text):
     lines = text.split("\n")
     for i, ln in enumerate(lines):
@@ -766,7 +788,24 @@ def pmc_of_pair(a, target, query, timeout_s):
 def run_single(a, torch, lib):
     from lastz_amd import lzgpu, seqio, lav as lavmod
     target, query = seqio.synth_pair(a.tlen, a.qlen, seed=1000)
-    rec, last = measure_pair(torch, lib, lzgpu, target, query, a.steps, a.warmup, not a.no_gapped)
+    rec, last = measure_pair(torch, lib, lzgpu, target, query, a.steps, a.warmup, a.full and not a.no_gapped)
+    if a.dump_outputs:
+        dump_hsps(a.dump_outputs, [("hsp_plus", last[0]), ("hsp_minus", last[1])])
+    head = {"metric": "Gbp-of-target aligned/sec (whole job, --nogapped HSP path, both strands)",
+            "value": rec["value"], "unit": "Gbp/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": rec["ms_per_step"], "ms_per_step_min": rec["ms_per_step_min"], "ms_per_step_median": rec["ms_per_step_median"],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "s32", "data": "synthetic",
+            "config": {"workload": ("BASELINE.json north_star size: " if a.north_star else "BASELINE.json configs[1]: ") +
+                                   "synthetic %d bp target vs %d bp query, 12-of-19 seed + 1 transition, "
+                                   "--nogapped, both strands" % (a.tlen, a.qlen),
+                       "tlen": a.tlen, "qlen": a.qlen, "scan_mode": rec["scan_mode"]},
+            "bp2_per_s": rec["bp2_per_s"], "hsps": rec["hsps"],
+            "counters_per_step": rec["counters_per_step"],
+            "kernel_ms_per_step": rec["kernel_ms_per_step"], "roofline": rec["roofline"]}
+    if not a.full:
+        emit(head)
+        return
     batch_res = rec.pop("_gapped_result", None)
     attach_traffic(rec, pmc_of_pair(a, target, query, 240 if a.tlen <= 60_000_000 else 480))
     gold = golden("bench200m.sha.json" if a.north_star else "bench50m.sha.json", a.tlen, a.qlen)
@@ -852,18 +891,7 @@ def run_single(a, torch, lib):
                     if ns_res is not None:
                         ns["parity"]["batch_alignments_vs_cli_lav"] = lavmod.compare(ns_res, lav2)
 
-    out = {"metric": "Gbp-of-target aligned/sec (whole job, --nogapped HSP path, both strands)",
-           "value": rec["value"], "unit": "Gbp/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
-           "ms_per_step": rec["ms_per_step"], "ms_per_step_min": rec["ms_per_step_min"], "ms_per_step_median": rec["ms_per_step_median"],
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "s32", "data": "synthetic",
-           "config": {"workload": ("BASELINE.json north_star size: " if a.north_star else "BASELINE.json configs[1]: ") +
-                                  "synthetic %d bp target vs %d bp query, 12-of-19 seed + 1 transition, "
-                                  "--nogapped, both strands" % (a.tlen, a.qlen),
-                      "tlen": a.tlen, "qlen": a.qlen, "scan_mode": rec["scan_mode"]},
-           "bp2_per_s": rec["bp2_per_s"], "hsps": rec["hsps"],
-           "counters_per_step": rec["counters_per_step"],
-           "kernel_ms_per_step": rec["kernel_ms_per_step"], "roofline": rec["roofline"], "parity": parity}
+    out = {**head, "parity": parity}
     if gapped is not None:
         out["gapped"] = gapped
     if "chain" in rec:
@@ -1149,9 +1177,11 @@ def run_multi(a, torch, lib, world, rank, local, dist, selfcheck=None):
                                            "gapped_gcups": (busy["dp_cells"] / (busy["gapped_s"] - busy["chain_s"]) / 1e9) if busy["gapped_s"] > busy["chain_s"] else None,
                                            "search_and_gapped_wall_s": phase["search_and_gapped"] / K})
     if rank == 0:
+        if a.dump_outputs and merged[0] is not None:
+            dump_hsps(a.dump_outputs, [("hsp_q%d_%s" % (qi, "minus" if strand else "plus"), hs) for (qi, strand), hs in merged[0]])
         kern_ms = {k: v["ms"] / K for k, v in prof.items()}
         cb = None
-        if not a.no_cpu_baseline:                           # the pristine reference on one host core, bounded sample of the same shape
+        if a.full and not a.no_cpu_baseline:                # the pristine reference on one host core, bounded sample of the same shape
             qs = seqio.synth_query(target[:a.cpu_sample], min(a.cpu_sample, ulen), seed=3100)
             cb = cpu_baseline(target, qs, a.qlen, min(a.cpu_sample, tlen, len(qs)), gapped=False, whole_host=False)
         nh = sum(len(v) for _, v in merged[0]) if merged[0] else 0
@@ -1225,12 +1255,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--tlen", type=int, default=50_000_000)
     ap.add_argument("--qlen", type=int, default=50_000_000)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: N = 1: the gapped, chain, parity, PMC, content, "
+                                                        "north-star, CLI and CPU-baseline legs; N > 1: the CPU baseline.  The --no-* options "
+                                                        "below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the HSP lists of the last one as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--cpu-sample", type=int, default=5_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-whole-host", action="store_true", help="cpu_baseline: the 1-core figure only")
-    ap.add_argument("--no-gapped", action="store_true", help="skip the gapped stage (N = 1: the configs[2] leg; N > 1: B3 of every unit)")
+    ap.add_argument("--no-gapped", action="store_true", help="skip the gapped stage (N = 1: the configs[2] leg of --full; N > 1: B3 of every unit)")
     ap.add_argument("--no-cli", action="store_true", help="skip the lastz CLI runs (wall clocks + LAV fingerprint)")
-    ap.add_argument("--no-north-star", action="store_true", help="N = 1: skip the 200 Mbp x 200 Mbp object of the default line")
+    ap.add_argument("--no-north-star", action="store_true", help="N = 1: skip the 200 Mbp x 200 Mbp object of the --full line")
     ap.add_argument("--no-content", action="store_true", help="N = 1: skip the soft-masked / IUPAC legs (scan modes 1 and 2)")
     ap.add_argument("--gapped", action="store_true", help="(default now; kept for old command lines)")
     ap.add_argument("--tlen-multi", type=int, default=200_000_000, help="N > 1: target length (configs[3]: 200 Mbp)")
@@ -1241,7 +1276,7 @@ def main():
     ap.add_argument("--chain", action="store_true", help="N > 1: --chain in front of the gapped stage (configs[4]'s shape): every unit's HSPs chained on the B3 thread, the chain extended")
     ap.add_argument("--force-multi", action="store_true", help="run the N > 1 code path with whatever WORLD_SIZE is (1 included)")
     ap.add_argument("--north-star", action="store_true", help="the whole N = 1 line at BASELINE.json's north_star size (200 Mbp x 200 Mbp; no CLI leg, "
-                                                              "1-core CPU baseline only); the default line carries the same pair as its north_star object")
+                                                              "1-core CPU baseline only); the --full line carries the same pair as its north_star object")
     ap.add_argument("--no-pmc", action="store_true", help="N = 1: no live rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE over a child process); roofline.traffic then replays the committed table")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pair-file", default=None, help=argparse.SUPPRESS)

@@ -1,4 +1,4 @@
-"""bench.py's host-side helpers that need no GPU: the one-line stdout contract and the committed gather ceiling."""
+"""bench.py's host-side helpers that need no GPU: the one-line stdout contract, the committed gather ceiling and the --dump-outputs writer."""
 import json
 import os
 import subprocess
@@ -31,3 +31,35 @@ def test_gather_ceiling_is_read_for_the_targets_footprint():
     assert 3000.0 < c200[0] < c50[0] < 8000.0               # random lines: below the streaming peak, lower from HBM than from the memory-side cache
     tab = json.load(open(os.path.join(H.ROOT, "profiles", "gather_ceiling.json")))
     assert [r["mib"] for r in tab["regions"]] == sorted(r["mib"] for r in tab["regions"])
+
+
+def test_dump_outputs_are_float64_whole_lists_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per list and HSP field plus the list's length; a list over its share of the byte budget is cut
+    to a seeded sample of its rows in list order -- the same rows every run, so that two builds compare output for output"""
+    sys.path.insert(0, H.ROOT)
+    import numpy as np
+    import bench
+    from lastz_amd import lzgpu
+    rng = np.random.default_rng(3)
+    big, small = (np.zeros(n, dtype=lzgpu.HSP_DTYPE) for n in (5000, 300))
+    for hs in (big, small):
+        for f in bench.HSP_FIELDS:
+            hs[f] = rng.integers(0, 1 << 31, len(hs))
+    big["pos1"] = np.arange(len(big))                                                               # (row numbers: which rows were kept)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * (8 + 1000 * 8 * len(bench.HSP_FIELDS)))     # 1000 rows per list
+    for d in ("a", "b"):
+        bench.dump_hsps(str(tmp_path / d), [("hsp_big", big), ("hsp_small", small)])
+    total = 0
+    for name, hs in (("hsp_big", big), ("hsp_small", small)):
+        assert np.load(tmp_path / "a" / (name + "_rows.npy")).tolist() == [len(hs)]
+        cols = {f: np.load(tmp_path / "a" / ("%s_%s.npy" % (name, f))) for f in bench.HSP_FIELDS}
+        for f, c in cols.items():
+            assert c.dtype == np.float64 and (c == np.load(tmp_path / "b" / ("%s_%s.npy" % (name, f)))).all()
+            total += c.nbytes
+        if len(hs) <= 1000:
+            assert all((cols[f] == hs[f]).all() for f in bench.HSP_FIELDS)
+        else:
+            picked = [int(v) for v in cols["pos1"]]
+            assert len(picked) == 1000 and picked == sorted(set(picked))
+            assert all((cols[f] == hs[f][picked]).all() for f in bench.HSP_FIELDS)
+    assert total <= bench.DUMP_BUDGET_BYTES

@@ -92,8 +92,7 @@ def test_two_ranks_equal_one(tmp_path):
     from oracle import lzo
     from lastz_amd import seqio
     import helpers as H
-    if not os.path.exists(os.path.join(H.ROOT, "tests", "emul", "libemul.so")):
-        pytest.skip("emulation harness not built (tests/test_emul_vs_oracle.py builds it)")
+    H.build_emul()                                            # tests/emul/libemul.so, which the ranks load (up to date: a no-op)
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = str(tmp_path / "merged.npy")
     mp.spawn(_worker, args=(2, port, H.ROOT, out), nprocs=2, join=True)

@@ -436,6 +436,32 @@ def test_resident_query_slots_and_torch_first_process(gpu):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """bench.py without --full: one JSON line with the contract's keys and none of the --full legs; --dump-outputs writes the HSP lists
+    of the last timed step, and they are the library's own for the same pair, field by field"""
+    import json, bench
+    d = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(H.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--tlen", "2000000", "--qlen", "2000000", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=H.ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = p.stdout.split("\n")
+    assert len(lines) == 2 and lines[1] == "", p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Gbp/s" and line["higher_is_better"] is True and line["dtype"] == "s32" and "Gbp-of-target" in line["metric"]
+    assert not {"parity", "gapped", "chain", "cli", "north_star", "content", "cpu_baseline", "configs2"} & set(line)
+    t, q = seqio.synth_pair(2_000_000, 2_000_000, seed=1000)
+    _, masked = H.scoring()
+    _prep(gpu, t)
+    want = [gpu.seed_hit_search(masked, q=qq) for qq in (q, seqio.revcomp(q))]
+    assert line["hsps"] == len(want[0]) + len(want[1]) > 100
+    for name, w in zip(("hsp_plus", "hsp_minus"), want):
+        assert np.load(d / (name + "_rows.npy")).tolist() == [len(w)]
+        for f in bench.HSP_FIELDS:
+            got = np.load(d / ("%s_%s.npy" % (name, f)))
+            assert got.dtype == np.float64 and (got == w[f]).all()
+
+
 def test_window_search_of_many_rectangles(gpu):
     """lzgpu_window_search: the table + search of src/tweener.c's in-between windows -- an exact 7-mer on
     rectangles of at most 20 kbp a side, no entropy -- for all windows in one launch, against the oracle run on the

@@ -2,7 +2,7 @@
 # A/B of environment settings on the seed bench: bash tools/ab.sh "VAR=1 OTHER=2" "VAR=0" ...   (one bench line each)
 cd $GRAFT_REPO_ROOT
 for cfg in "$@"; do
-  env $cfg python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-cli --no-gapped > /tmp/o.json 2>/tmp/e.txt
+  env $cfg python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-cli --no-gapped > /tmp/o.json 2>/tmp/e.txt
   CFG="$cfg" python - <<'PY'
 import json, os
 try:

@@ -8,7 +8,7 @@ for spec in "$@"; do
   tag=${spec%%:*}; envs=""; [ "$spec" != "$tag" ] && envs=$(echo "${spec#*:}" | tr ',' ' ')
   lib=$PWD/lastz_amd/liblzgpu.so; [ "$tag" != "default" ] && lib=$PWD/lastz_amd/liblzgpu_$tag.so
   name=$(echo "$spec" | tr ':=,' '___')
-  env LZGPU_LIB=$lib $envs timeout 300 python bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-cli --no-north-star --no-content ${BENCH_ARGS:---no-gapped} > $O/bench_$name.json 2> $O/bench_$name.err
+  env LZGPU_LIB=$lib $envs timeout 300 python bench.py --full --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-cli --no-north-star --no-content ${BENCH_ARGS:---no-gapped} > $O/bench_$name.json 2> $O/bench_$name.err
   NAME=$name O=$O python - <<'PY'
 import json, os
 name = os.environ["NAME"]; O = os.environ["O"]

@@ -5,7 +5,7 @@ O=$1; shift; mkdir -p $O
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 for tag in "$@"; do
   lib=$PWD/lastz_amd/liblzgpu.so; [ "$tag" != "default" ] && lib=$PWD/lastz_amd/liblzgpu_$tag.so
-  LZGPU_LIB=$lib timeout 600 python bench.py --north-star --steps 2 --warmup 1 --no-cpu-baseline --no-content --no-cli --no-gapped > $O/ns_$tag.json 2> $O/ns_$tag.err
+  LZGPU_LIB=$lib timeout 600 python bench.py --full --north-star --steps 2 --warmup 1 --no-cpu-baseline --no-content --no-cli --no-gapped > $O/ns_$tag.json 2> $O/ns_$tag.err
   TAG=$tag O=$O python - <<'PY'
 import json, os
 try:

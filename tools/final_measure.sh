@@ -1,22 +1,22 @@
 #!/bin/bash
 # One GPU-box pass that produces everything profiles/ needs for a round.  usage: bash tools/final_measure.sh <tag>; writes under gpurun_out/<tag>/.
-# Order matters: the driver's bench command runs FIRST, as the driver runs it -- the first process on a fresh box (k_fill_hits2 and
+# Order matters: the driver's bench command (here with --full: the same timed steps first, then every leg) runs FIRST -- the first process on a fresh box (k_fill_hits2 and
 # k_count_hits are 30-40 % slower in the processes that follow another one on the same box: profiles/r05_fill_kernel_process_to_process.txt).
 set -u
 O=gpurun_out/${1:-final}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 export LZGPU_REQUIRE_GPU=1
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; echo
+timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; echo
 timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; tail -2 $O/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
 LEGS="--no-cpu-baseline --no-cli --no-north-star --no-content --no-pmc"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --gpus 1 --steps 20 --warmup 5 $LEGS > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --gpus 1 --steps 20 --warmup 5 $LEGS > $O/bench_under_rocprof.json 2> $O/rocprof_stats.err
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats200 -- python bench.py --north-star --steps 2 --warmup 1 --no-cpu-baseline --no-content --no-pmc > $O/bench_200m_under_rocprof.json 2> $O/rocprof_stats200.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats200 -- python bench.py --full --north-star --steps 2 --warmup 1 --no-cpu-baseline --no-content --no-pmc > $O/bench_200m_under_rocprof.json 2> $O/rocprof_stats200.err
 find $O/stats200 -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_200m.csv \;
-# the committed PMC table (what bench.py --no-pmc replays; the default run collects its own)
-timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python bench.py --steps 1 --warmup 0 $LEGS > /dev/null 2>&1
-timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python bench.py --steps 1 --warmup 0 $LEGS > /dev/null 2>&1
+# the committed PMC table (what bench.py --no-pmc replays; a --full run collects its own)
+timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_f -- python bench.py --full --steps 1 --warmup 0 $LEGS > /dev/null 2>&1
+timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_w -- python bench.py --full --steps 1 --warmup 0 $LEGS > /dev/null 2>&1
 python tools/pmc_fetch_write.py "$O/pmc_f/**/*counter_collection.csv" "$O/pmc_w/**/*counter_collection.csv" > $O/pmc_fetch_write.csv
 head -12 $O/pmc_fetch_write.csv; head -14 $O/kernel_stats.csv | cut -c1-60,400-
 rm -rf $O/stats $O/stats200 $O/pmc_f $O/pmc_w

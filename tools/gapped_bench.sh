@@ -4,7 +4,7 @@ set -u
 O=$1; N=${2:-3}; mkdir -p $O
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 for k in $(seq 1 $N); do
-timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-cli --no-north-star --no-content > $O/gbench_$k.json 2> $O/gbench_$k.err
+timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-cli --no-north-star --no-content > $O/gbench_$k.json 2> $O/gbench_$k.err
 python - <<PY
 import json
 d = json.load(open("$O/gbench_$k.json")); g = d["gapped"]

@@ -4,7 +4,7 @@ set -u
 O=$1; N=${2:-2}; mkdir -p $O
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 for k in $(seq 1 $N); do
-LZGPU_HOSTPROF=1 timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-cli --no-north-star --no-content > $O/bench_$k.json 2> $O/bench_$k.err
+LZGPU_HOSTPROF=1 timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-cli --no-north-star --no-content > $O/bench_$k.json 2> $O/bench_$k.err
 grep -a "hostprof\] gapped" $O/bench_$k.err | tail -3
 python - <<PY
 import json

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 export LZGPU_REQUIRE_GPU=1
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; tail -6 $O/pytest_gpu.txt
 if [ $# -gt 0 ]; then
-  timeout 900 python bench.py "$@" > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
+  timeout 900 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.err
   python - <<PY
 import json
 d = json.load(open("$O/bench.json"))
