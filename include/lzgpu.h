@@ -171,6 +171,26 @@ typedef struct lz_hsp {            /* exactly what hp->reporter receives (src/se
  * target position descending).  *out is released with lzgpu_free(). */
 int lzgpu_seed_hit_search(const lz_search_args* args, lz_hsp** out, uint64_t* n_out);
 
+/* ---- B2 for a self-comparison (lastz --self, --band) ----------------------------------------
+ * seed_hit_search with selfCompare set (src/seed_search.c:322-574): the raw hits on or below the diagonal
+ * (seed_hit_below_diagonal, :2052-2235), and with a band those more than band_width off the main diagonal, are
+ * dropped before they are processed (:841-848, 903-908); everything else, the counters included, is what
+ * lzgpu_seed_hit_search does with the hits that remain.  The query is the target itself or its reverse complement:
+ * its length must equal the target's.  same_strand = (seq1->revCompFlags == seq2->revCompFlags) (:373).  The
+ * separators of a [multi] sequence are its partitions' sepBefore values plus the final NUL, as lz_gapped_args takes
+ * them; both counts 0 for a sequence without partitions.  A band with opposite strands, separator counts that differ
+ * (or equal 1, or are not ascending inside the sequence), a query of another length, bucket owners
+ * (lzgpu_set_bucket_owner) or LZGPU_FILL_SHUFFLE return LZGPU_NH_UNSUPPORTED before any work is done. */
+typedef struct lz_self_args {
+    int32_t         same_strand;   /* selfCompare && seq1->revCompFlags == seq2->revCompFlags        */
+    uint32_t        band_width;    /* --band (0: none); only with same_strand                        */
+    const uint32_t* sep1;          /* seq1's separators (NULL / 0 when unpartitioned)                */
+    uint32_t        n_sep1;
+    const uint32_t* sep2;          /* seq2's                                                          */
+    uint32_t        n_sep2;
+} lz_self_args;
+int lzgpu_seed_hit_search_self(const lz_search_args* args, const lz_self_args* self, lz_hsp** out, uint64_t* n_out);
+
 /* ---- B1 + B2 for many small rectangles of the two sequences at once ----------------------------
  * What src/tweener.c:769-829 (bounded_align) does for every in-between window of `lastz --inner=<score>`:
  * build_seed_position_table on target[t_off, t_off + t_len) with the inner seed, seed_hit_search of

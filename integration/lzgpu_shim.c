@@ -116,7 +116,7 @@ __attribute__((constructor)) static void unlocked_stdout (void)
 /* ... and a chunk for the search at hand: about an eighth of the hits it should find (random sequence: probes x target
  * words x query words / 4^weight), between 2^26 and 2^30 -- the 200 Mbp pair in 2^28 chunks is 231 chunks a strand,
  * 7.1-8.0 s for the run against 6.4 s with 2^30 */
-static void chunk_for (seed* hitSeed, unspos tLen, unspos qLen)
+static void chunk_for (seed* hitSeed, unspos tLen, unspos qLen, int selfCompare)
 	{
 	double est;
 	int    probes = 1, nf = 0, lg;
@@ -124,6 +124,7 @@ static void chunk_for (seed* hitSeed, unspos tLen, unspos qLen)
 	if ((hitSeed->withTrans != 0) && (hitSeed->transFlips != NULL)) while (hitSeed->transFlips[nf] != 0) nf++;
 	if (hitSeed->withTrans == 1) probes = 1 + nf;  else if (hitSeed->withTrans >= 2) probes = 1 + nf + nf * (nf - 1) / 2;
 	est = ((double) probes) * ((double) tLen) * ((double) qLen) / ((double) (1ull << hitSeed->weight)) / 8.0;
+	if (selfCompare) est /= 2.0;                                /* a self-comparison keeps about half of them (the hits above the diagonal) */
 	for (lg=26 ; (lg < 30) && (((double) (1ull << lg)) < est) ; lg++) ;
 	lzgpu_set_hit_capacity (1ull << lg);
 	}
@@ -288,6 +289,17 @@ static uint32_t* partition_separators (seq* s, uint32_t* n)
 	for (i=0 ; i<=sp->len ; i++) v[i] = sp->p[i].sepBefore;      /* (entry len: the final NUL) */
 	*n = sp->len + 1;
 	return v;
+	}
+
+/* the separators stand for sepAfter too (partition i ends where i + 1 begins): not so after --separator cut a record at a
+   run of separator characters (src/sequences.c:6225-6272) */
+static int partitions_abut (seq* s)
+	{
+	seqpartition* sp = &s->partition;
+	u32           i;
+	if (sp->p == NULL) return true;
+	for (i=0 ; i<sp->len ; i++) if (sp->p[i].sepAfter != sp->p[i+1].sepBefore) return false;
+	return true;
 	}
 
 /* ---- the tweener's in-between windows (lastz --inner=<score>, src/tweener.c), SURVEY 8(f) N3 ----
@@ -545,7 +557,7 @@ u64 seed_hit_search
 	if ((pt != devTable) || (devTable == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
 	 || (processor != process_for_simple_hit) || (hp->gfExtend != gfexXDrop)
 	 || (hp->hspThreshold.t != 'S') || (hp->posFilter) || (hp->minMatches >= 0) || (hp->reportEntropy)
-	 || (selfCompare) || (bandWidth != 0) || (searchLimit != 0)
+	 || ((!selfCompare) && (bandWidth != 0)) || (searchLimit != 0)
 	 || (seq2->fileType == seq_type_qdna) || (hp->seq1 != seq1) || (hp->seq2 != seq2)
 	 || (memcmp (upperCharToBits, devCharToBits, 256) != 0)
 	 || (seed_search_dbgDumpRawHits) || (seed_search_dbgShowHits) || (seed_search_dbgShowCoverage))
@@ -553,15 +565,32 @@ u64 seed_hit_search
 		  return ref_seed_hit_search (seq1, pt, seq2, start, end, selfCompare, upperCharToBits, hitSeed,
 		                              searchLimit, reportSearchLimit, bandWidth, processor, processorInfo); }
 
-	chunk_for (hitSeed, seq1->len, seq2->len);
+	chunk_for (hitSeed, seq1->len, seq2->len, selfCompare);
 	memset (&a, 0, sizeof(a));
 	a.query = seq2->v;  a.qlen = seq2->len;  a.query_slot = -1;
 	a.start = start;    a.end = end;
 	a.sub   = (const int32_t*) hp->scoring->sub;
 	a.xdrop = hp->xDrop;  a.hsp_threshold = hp->hspThreshold.s;  a.entropic = hp->entropicHsp;  a.extend = 1;
 
-	rc = lzgpu_seed_hit_search (&a, &h, &n);
-	if (rc < 0) suicidef ("lzgpu_seed_hit_search: %s", lzgpu_last_error());
+	if (selfCompare)                                            /* --self (and --band): the hits seed_hit_below_diagonal drops, dropped on the device */
+		{
+		lz_self_args sa;
+		uint32_t*    sep1, *sep2;
+		memset (&sa, 0, sizeof(sa));
+		sa.same_strand = (seq1->revCompFlags == seq2->revCompFlags);      /* src/seed_search.c:373 */
+		sa.band_width  = (sa.same_strand)? bandWidth : 0;                  /* (the band applies to the same strand only, :844) */
+		sep1 = partition_separators (seq1, &sa.n_sep1);  sa.sep1 = sep1;
+		sep2 = partition_separators (seq2, &sa.n_sep2);  sa.sep2 = sep2;
+		if ((!partitions_abut (seq1)) || (!partitions_abut (seq2))) rc = LZGPU_NH_UNSUPPORTED;
+		else rc = lzgpu_seed_hit_search_self (&a, &sa, &h, &n);
+		free (sep1);  free (sep2);
+		if (rc < 0) suicidef ("lzgpu_seed_hit_search_self: %s", lzgpu_last_error());
+		}
+	else
+		{
+		rc = lzgpu_seed_hit_search (&a, &h, &n);
+		if (rc < 0) suicidef ("lzgpu_seed_hit_search: %s", lzgpu_last_error());
+		}
 	if (rc > 0)
 		{ note ("search", "declined, reference path");  host_table_needed (pt);
 		  return ref_seed_hit_search (seq1, pt, seq2, start, end, selfCompare, upperCharToBits, hitSeed,

@@ -102,6 +102,136 @@ LZ_HD void lz_fill_hits_at(const u8* qcode, u32 pos2, const LzSeedDev& sd, const
     }
 }
 
+// ---- self-comparison (lastz --self, --band): the raw hits seed_hit_search drops before the processor sees them
+// (find_table_matches / _resolve, src/seed_search.c:841-848, 903-908; sameStrand :373; seed_hit_below_diagonal
+// :2052-2235).  pos1 / pos2 are hit END positions, L the seed length, and a hit is dropped when
+//   same strand:                 pos1 >= pos2, or (band w > 0) pos2 - pos1 > w
+//   opposite, seq2 unpartitioned: p1 >= p2 with p1 = pos1 - L, p2 = (len2 - 1) - (pos2 - L)
+//   opposite, partitioned:        partition ix1 of p1 in seq1, ix2 of q = pos2 - L in seq2; ix1 >= ix2 if they differ,
+//                                 else p1 >= (sepBefore2[ix2] + sepAfter2[ix2]) - q.
+// For a fixed pos2 the hits kept are always an interval [lo, hi) of pos1 (lz_self_bounds): in the first two cases
+// directly; in the third, partitions lie along seq1 in index order, so "ix1 < ix2" is "p1 < sep1[ix2]" and "ix1 == ix2
+// and p1 < thr" is "sep1[ix2] < p1 < min(thr, sep1[ix2 + 1])"; a hit's window holds no separator (the NULs are not
+// seed bytes), so p1 is never a separator itself, and the union of the two is p1 < clamp(thr, sep1[ix2], sep1[ix2 + 1]).
+// A word's list in the position table is sorted by DESCENDING pos1 (k_table_words), so the kept hits of a list are
+// one contiguous sub-run of it (lz_clip_run).  Separators are the partitions' sepBefore values plus the final NUL
+// (n = partitions + 1, sepAfter[i] == sep[i + 1]), as lzgpu_gapped_extend takes them.
+#define LZ_SELF_OFF       0
+#define LZ_SELF_SAME      1           // same strand, optional band
+#define LZ_SELF_OPP       2           // opposite strands, seq2 unpartitioned
+#define LZ_SELF_OPP_PARTS 3           // opposite strands, [multi]
+struct LzSelfDev {
+    u32 mode, L, len2, band;
+    const u32* sep1; u32 n_sep1;
+    const u32* sep2; u32 n_sep2;
+};
+
+// number of separators <= x (the partition of a non-separator position x is this minus one)
+LZ_HD u32 lz_sep_rank(const u32* sep, u32 n, u32 x)
+{
+    u32 a = 0, b = n;
+    while (a < b) { const u32 m = (a + b) >> 1; if (sep[m] <= x) a = m + 1; else b = m; }
+    return a;
+}
+
+// [lo, hi) of the pos1 values whose hit with the query word ending at pos2 survives
+LZ_HD void lz_self_bounds(const LzSelfDev& s, u32 pos2, u32& lo, u32& hi)
+{
+    lo = 0;
+    if (s.mode == LZ_SELF_SAME) {                               // :2183-2188, band :844-845
+        hi = pos2;
+        if (s.band > 0 && pos2 > s.band) lo = pos2 - s.band;
+    } else if (s.mode == LZ_SELF_OPP) {                         // :2195-2203: p1 < (len2 - 1) - (pos2 - L)
+        hi = (s.len2 - pos2) + 2u * s.L - 1u;                   // (pos2 <= len2)
+    } else if (s.mode == LZ_SELF_OPP_PARTS) {                   // :2207-2234
+        const u32 q = pos2 - s.L;
+        u32 ix = lz_sep_rank(s.sep2, s.n_sep2, q);
+        ix = ix > 0 ? ix - 1u : 0u;
+        if (ix > s.n_sep2 - 2u) ix = s.n_sep2 - 2u;             // (q inside a partition: never taken)
+        const u32 thr = s.sep2[ix] + s.sep2[ix + 1] - q;
+        const u32 a = s.sep1[ix], b = s.sep1[ix + 1];
+        hi = (thr < a ? a : thr > b ? b : thr) + s.L;
+    } else {
+        hi = 0xFFFFFFFFu;
+    }
+}
+
+// Shrink the list wpos[a, a + len) (descending positions) to the entries in [lo, hi): two searches, for the number of
+// leading entries >= hi and the number >= lo (the latter only when lo > 0), by powers of two from the largest one that
+// fits the longest list down.  N lists at once with one schedule of steps, so that every step has the loads of all N
+// lists in flight together.
+template <int N>
+LZ_HD void lz_clip_runs(const u32* wpos, u32* a, u32* len, u32 lo, u32 hi)
+{
+    u32 kh[N], kl[N], m = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int p = 0; p < N; p++) { kh[p] = 0; kl[p] = 0; m |= len[p]; }
+    for (u32 s = m ? 1u << (31 - __builtin_clz(m)) : 0u; s; s >>= 1) {
+        u32 vh[N], vl[N];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int p = 0; p < N; p++) {
+            vh[p] = kh[p] + s <= len[p] ? wpos[a[p] + kh[p] + s - 1u] : 0u;
+            vl[p] = lo && kl[p] + s <= len[p] ? wpos[a[p] + kl[p] + s - 1u] : 0u;
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+        for (int p = 0; p < N; p++) {
+            if (kh[p] + s <= len[p] && vh[p] >= hi) kh[p] += s;
+            if (lo && kl[p] + s <= len[p] && vl[p] >= lo) kl[p] += s;
+        }
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int p = 0; p < N; p++) {
+        const u32 e = lo ? kl[p] : len[p];
+        a[p] += kh[p];
+        len[p] = e > kh[p] ? e - kh[p] : 0u;
+    }
+}
+// one list: [a, b) -> [a', a' + len')
+LZ_HD void lz_clip_run(const u32* wpos, u32 a, u32 b, u32 lo, u32 hi, u32& a_out, u32& len_out)
+{
+    u32 aa[1] = { a }, ll[1] = { b - a };
+    lz_clip_runs<1>(wpos, aa, ll, lo, hi);
+    a_out = aa[0]; len_out = ll[0];
+}
+
+// lz_count_hits_at / lz_fill_hits_at for a self-comparison: the surviving hits only, in the same order
+LZ_HD u32 lz_count_hits_self_at(const u8* qcode, u32 pos2, u32 lo, const LzSeedDev& sd, const LzSelfDev& self,
+                                const u32* wstart, const u32* wpos, bool& valid, u32& packed)
+{
+    valid = false;
+    if (pos2 < lo + (u32)sd.length) return 0;
+    if (!lz_window_word(qcode, pos2, sd, packed)) return 0;
+    valid = true;
+    u32 blo, bhi; lz_self_bounds(self, pos2, blo, bhi);
+    u32 n = 0;
+    for (int p = 0; p < sd.nprobes; p++) {
+        const u32 w = packed ^ sd.probe_xor[p];
+        u32 a, l; lz_clip_run(wpos, wstart[w], wstart[w + 1], blo, bhi, a, l);
+        n += l;
+    }
+    return n;
+}
+LZ_HD void lz_fill_hits_self_at(const u8* qcode, u32 pos2, const LzSeedDev& sd, const LzSelfDev& self,
+                                const u32* wstart, const u32* wpos, u64* out)
+{
+    u32 packed;
+    if (!lz_window_word(qcode, pos2, sd, packed)) return;
+    u32 blo, bhi; lz_self_bounds(self, pos2, blo, bhi);
+    for (int p = 0; p < sd.nprobes; p++) {
+        const u32 w = packed ^ sd.probe_xor[p];
+        u32 a, l; lz_clip_run(wpos, wstart[w], wstart[w + 1], blo, bhi, a, l);
+        for (u32 j = a; j < a + l; j++) *out++ = lz_hit_key(wpos[j], pos2);
+    }
+}
+
 struct LzExtendParams {
     const u8* tcode; u32 tlen;     // target codes (tcode[0] is base 0; LZ_SEQ_PAD readable bytes either side)
     const u8* qcode; u32 qlen;

@@ -101,6 +101,8 @@ struct LzCtx {
     DevBuf dev_counters;            // u64[8]
     DevBuf tb_keys, tb_vals, tb_keys2, tb_vals2;   // table build scratch
     u32 n_owners = 1, owner = 0;      // bucket ownership (lzgpu_set_bucket_owner)
+    LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self); mode LZ_SELF_OFF otherwise
+    DevBuf self_sep;                  // its separators on the device: sep1, then sep2
     std::vector<u64> last_order;      // two sort words per HSP of the last search
     int min_scan_mode = 0;            // lzgpu_set_scan_mode
     int last_scan_mode = -1;          // phase-A scan mode of the last search (0/1: look-up tables without/with special masks, 2: byte codes)
@@ -124,10 +126,10 @@ int lzk_encode(LzCtx& c, const u8* raw, u8* code, u32 len, const u8* cls256_dev,
 int lzk_pack_nibbles(LzCtx& c, const u8* code_alloc, u8* nib, size_t nbytes);
 int lzk_table_build(LzCtx& c);
 int lzk_table_export(LzCtx& c, u32* last_dev, u32* prev_dev, u32 prev_entries);
-int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk, u32* iv, u32* sk, u32* sv, u64* valid_words_dev);   // honours c.n_owners / c.owner
+int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk, u32* iv, u32* sk, u32* sv, u64* valid_words_dev);   // honours c.n_owners / c.owner and c.self
 int lzk_scan_counts(LzCtx& c, const u32* cnt, u64* off, u32 n);
 int lzk_sample_offsets(LzCtx& c, const u64* off, const u32* cnt, u32 n, u32 stride, u32 ns, u64* out);
-int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64* keys, hipStream_t st);
+int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64* keys, hipStream_t st);   // likewise
 int lzk_hsp_match_counts(LzCtx& c, const LzHspRec* recs, const u32* n_rec_dev, u32 cap, u32 launch_for,
                          const u8* traw, const u8* qraw, const u8* tcode, const u8* qcode, u32* counts, hipStream_t s);
 struct LzLutParams; struct LzLutEntry;

@@ -497,7 +497,8 @@ struct HostProf {
 };
 static HostProf g_hp;
 
-extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
+// the search proper; with c.self.mode != LZ_SELF_OFF the count and fill kernels drop the hits a self-comparison drops
+static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
 {
     int rc = require_init(); if (rc) return rc;
     LzCtx& c = g_ctx;
@@ -771,6 +772,58 @@ extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint
     g_hp.lap(6, "host finish (order+entropy)");
     *out = res; *n_out = fin.size();
     return 0;
+}
+
+extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
+{
+    return seed_search(a, out, n_out);
+}
+
+// Self-comparison (lastz --self, --band).  Every raw hit the reference drops (src/seed_search.c:841-848, 903-908,
+// 2052-2235) lies outside an interval of target positions that depends on the query position alone (lz_common.hpp,
+// lz_self_bounds), and the table's lists are sorted by position: the count and fill kernels clip each list to that
+// interval, and everything after them runs unchanged on the surviving hits.
+extern "C" int lzgpu_seed_hit_search_self(const lz_search_args* a, const lz_self_args* s, lz_hsp** out, uint64_t* n_out)
+{
+    int rc = require_init(); if (rc) return rc;
+    LzCtx& c = g_ctx;
+    if (!a || !s || !out || !n_out || !a->sub) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    *out = nullptr; *n_out = 0;
+    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "lzgpu_table_prepare has not been called");
+    u32 qlen = a->qlen;
+    if (!a->query) {
+        const SeqSlot* qs = a->query_slot < 0 ? nullptr : lz_query_slot(c, a->query_slot, false);
+        if (!qs) return lz_fail(LZGPU_ERR_ARG, "query slot %d is empty", a->query_slot);
+        qlen = qs->len;
+    }
+    // what the kernels assume (seed_hit_below_diagonal's note (1), :2068-2070): one sequence against itself
+    if (qlen != c.geom.tlen) return LZGPU_NH_UNSUPPORTED;
+    if (s->band_width != 0 && !s->same_strand) return LZGPU_NH_UNSUPPORTED;      // (the reference bands the same strand only, :844)
+    if (s->n_sep1 != s->n_sep2 || s->n_sep1 == 1) return LZGPU_NH_UNSUPPORTED;
+    if (s->n_sep1 && (!s->sep1 || !s->sep2)) return LZGPU_NH_UNSUPPORTED;
+    for (u32 k = 0; k < s->n_sep1; k++) {                                         // ascending, inside the sequence
+        if (s->sep1[k] > qlen || s->sep2[k] > qlen) return LZGPU_NH_UNSUPPORTED;
+        if (k && (s->sep1[k] <= s->sep1[k - 1] || s->sep2[k] <= s->sep2[k - 1])) return LZGPU_NH_UNSUPPORTED;
+    }
+    // only k_count_sorted_self and k_fill_hits2<true> clip: not with bucket owners or the shuffle fill
+    if (c.n_owners > 1 || getenv("LZGPU_FILL_SHUFFLE") != nullptr) return LZGPU_NH_UNSUPPORTED;
+
+    LzSelfDev sd = {};
+    sd.L = (u32)c.seed.length; sd.len2 = qlen; sd.band = s->same_strand ? s->band_width : 0u;
+    sd.mode = s->same_strand ? LZ_SELF_SAME : s->n_sep2 ? LZ_SELF_OPP_PARTS : LZ_SELF_OPP;
+    if (sd.mode == LZ_SELF_OPP_PARTS) {
+        const size_t n = (size_t)s->n_sep1;
+        if ((rc = c.self_sep.ensure(2 * n * 4))) return rc;
+        LZ_HIP(hipMemcpyAsync(c.self_sep.as<u32>(), s->sep1, n * 4, hipMemcpyHostToDevice, c.stream));
+        LZ_HIP(hipMemcpyAsync(c.self_sep.as<u32>() + n, s->sep2, n * 4, hipMemcpyHostToDevice, c.stream));
+        LZ_HIP(hipStreamSynchronize(c.stream));
+        sd.sep1 = c.self_sep.as<u32>(); sd.n_sep1 = s->n_sep1;
+        sd.sep2 = c.self_sep.as<u32>() + n; sd.n_sep2 = s->n_sep2;
+    }
+    c.self = sd;
+    rc = seed_search(a, out, n_out);
+    c.self = LzSelfDev{};
+    return rc;
 }
 
 // ------------------------------------------------------------------------------ B1 + B2 of many windows (N3)

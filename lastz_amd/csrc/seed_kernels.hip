@@ -278,6 +278,40 @@ k_count_sorted_owned(const u32* __restrict__ sk, const u32* __restrict__ sv, u32
     cnt[i] = c;
 }
 
+// self-comparison (lz_common.hpp, LzSelfDev): only the hits in [lo, hi) of pos1 count, and every list is clipped to them
+// with two binary searches over its (descending) positions -- so, unlike k_count_sorted, the positions are read.  The 16
+// probes of a group go through their searches in lock step (lz_clip_runs): their bounds and then each step's 16 loads are
+// in flight together.
+#define LZ_SELF_GROUP 16
+__global__ void __launch_bounds__(LZ_TPB)
+k_count_sorted_self(const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, u32 lo, LzSeedDev sd,
+                    const u32* __restrict__ wstart, const u32* __restrict__ wpos, u32* __restrict__ cnt, LzSelfDev self)
+{
+    const u32 j = blockIdx.x * LZ_TPB + threadIdx.x;
+    if (j >= n) return;
+    const u32 w0 = sk[j] & ((2u << sd.weight) - 1u);
+    if (w0 >> sd.weight) return;
+    const u32 i = sv[j], pos2 = lo + i + 1;
+    u32 blo, bhi;
+    lz_self_bounds(self, pos2, blo, bhi);
+    u32 c = 0;
+    for (int r = 0; r < sd.nprobes; r += LZ_SELF_GROUP) {
+        u32 a[LZ_SELF_GROUP], len[LZ_SELF_GROUP];
+#pragma unroll
+        for (int p = 0; p < LZ_SELF_GROUP; p++) {
+            const bool on = r + p < sd.nprobes;
+            const u32 w = on ? (w0 ^ sd.probe_xor[(r + p) & (LZ_MAX_PROBES - 1)]) : 0u;
+            a[p] = wstart[w]; len[p] = wstart[w + 1];
+        }
+#pragma unroll
+        for (int p = 0; p < LZ_SELF_GROUP; p++) { const bool on = r + p < sd.nprobes; len[p] = on ? len[p] - a[p] : 0u; }
+        lz_clip_runs<LZ_SELF_GROUP>(wpos, a, len, blo, bhi);
+#pragma unroll
+        for (int p = 0; p < LZ_SELF_GROUP; p++) c += len[p];
+    }
+    cnt[i] = c;
+}
+
 int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk, u32* iv, u32* sk, u32* sv, u64* valid_words_dev)
 {
     const u32 n = hi - lo;
@@ -314,7 +348,10 @@ int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk,
     if ((rc = c.blk_start.ensure(130 * 8))) return rc;
     hipLaunchKernelGGL(k_block_starts, dim3(1), dim3(192), 0, c.stream, sk, n, kbits, 1u << c.seed.weight, c.blk_count, c.blk_start.as<u64>(), valid_words_dev);
     c.timer.begin("k_count_hits", c.stream);
-    if (c.n_owners > 1)
+    if (c.self.mode != LZ_SELF_OFF)
+        hipLaunchKernelGGL(k_count_sorted_self, dim3((n + LZ_TPB - 1) / LZ_TPB), dim3(LZ_TPB), 0, c.stream,
+                           sk, sv, n, lo, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), cnt, c.self);
+    else if (c.n_owners > 1)
         hipLaunchKernelGGL(k_count_sorted_owned, dim3((n + LZ_TPB - 1) / LZ_TPB), dim3(LZ_TPB), 0, c.stream,
                            sk, sv, n, lo, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), cnt, c.n_owners, c.owner);
     else
@@ -484,11 +521,14 @@ __device__ __forceinline__ u32 lz_dpp_u32(u32 ident, u32 src) { return (u32)__bu
     v = OP(lz_dpp_u32<0x143, 0xc, 0xf>(0u, v), v);
 __device__ __forceinline__ u32 lz_uadd(u32 a, u32 b) { return a + b; }
 __device__ __forceinline__ u32 lz_umax(u32 a, u32 b) { return a > b ? a : b; }
+// SELF: a self-comparison (lz_common.hpp, LzSelfDev): step 1 clips every list to the hits that survive, before the
+// wave scan (k_count_sorted_self counted the same); the rest of the kernel is the same code.
+template <bool SELF>
 __global__ void __launch_bounds__(LZ_TPB)
 k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
              const u32* __restrict__ wstart, const u32* __restrict__ wpos,
              const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, const u64* __restrict__ off,
-             u64 base, u64* __restrict__ keys)
+             u64 base, u64* __restrict__ keys, LzSelfDev self)
 {
     __shared__ LzFill2Wave shw[LZ_TPB / 64];
     LzFill2Wave& sh = shw[threadIdx.x >> 6];
@@ -500,6 +540,8 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
     if (!__ballot(in)) return;                                  // (wave-uniform: nothing of this chunk among the wave's entries)
     const u32 dbase = in ? (u32)(off[i_l] - base) : 0u;         // (hit indices inside a chunk are 32-bit)
     const u32 pos2 = lo + i_l + 1u;
+    u32 slo = 0, shi = 0;
+    if (SELF) lz_self_bounds(self, pos2, slo, shi);
     u32 carry = 0;                                              // hits of the lane's position in the probe groups already done
     for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {       // uniform trip count
         // ---- 1. bounds of the lane's lists
@@ -515,7 +557,13 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 #pragma unroll
         for (int p = 0; p < LZ_FILL_GROUP; p++) {
             const bool on = in && r + p < sd.nprobes;
-            len[p] = on ? len[p] - la[p] : 0u; total += len[p];
+            len[p] = on ? len[p] - la[p] : 0u;
+            if (!SELF) total += len[p];
+        }
+        if (SELF) {
+            lz_clip_runs<LZ_FILL_GROUP>(wpos, la, len, slo, shi);
+#pragma unroll
+            for (int p = 0; p < LZ_FILL_GROUP; p++) total += len[p];
         }
         u32 inc = total;
         LZ_WAVE_SCAN_U32(inc, total, lz_uadd)
@@ -598,7 +646,11 @@ int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv
         if (n == 0) return 0;
     }
     c.timer.begin("k_fill_hits", st);
-    if (c.n_owners > 1)
+    if (c.self.mode != LZ_SELF_OFF) {
+        // (lzgpu_seed_hit_search_self declines bucket owners and LZGPU_FILL_SHUFFLE: only this kernel clips)
+        hipLaunchKernelGGL(k_fill_hits2<true>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
+                           lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, c.self);
+    } else if (c.n_owners > 1)
         hipLaunchKernelGGL(k_fill_hits<true>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
                            lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, c.n_owners, c.owner);
     else {
@@ -607,8 +659,8 @@ int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv
             hipLaunchKernelGGL(k_fill_hits<false>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
                                lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, 1u, 0u);
         else
-            hipLaunchKernelGGL(k_fill_hits2, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
-                               lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys);
+            hipLaunchKernelGGL(k_fill_hits2<false>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
+                               lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, LzSelfDev{});
     }
     c.timer.end(st);
     LZ_HIP(hipGetLastError());

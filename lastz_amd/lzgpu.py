@@ -51,6 +51,11 @@ class WindowSearchArgs(C.Structure):
                 ("windows", C.c_void_p), ("n_windows", C.c_uint32)]
 
 
+class SelfArgs(C.Structure):
+    _fields_ = [("same_strand", C.c_int32), ("band_width", C.c_uint32), ("sep1", C.c_void_p), ("n_sep1", C.c_uint32),
+                ("sep2", C.c_void_p), ("n_sep2", C.c_uint32)]
+
+
 class Counters(C.Structure):
     _fields_ = [("words", C.c_uint64), ("raw_hits", C.c_uint64), ("extensions", C.c_uint64),
                 ("bp_extended", C.c_uint64), ("hsps", C.c_uint64), ("dp_cells", C.c_uint64),
@@ -67,7 +72,7 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
            "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_table_num_words",
            "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_device_copy",
-           "lzgpu_seed_hit_search", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
+           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
            "lzgpu_set_bucket_owner", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
@@ -99,6 +104,8 @@ class Lib:
         self.px = prefix
         f = self._f
         f("seed_hit_search").argtypes = [C.POINTER(SearchArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        if prefix == "lzgpu_":
+            self.L.lzgpu_seed_hit_search_self.argtypes = [C.POINTER(SearchArgs), C.POINTER(SelfArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         f("table_prepare").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(SeedDesc), C.c_uint32]
         f("set_hit_capacity").argtypes = [C.c_uint64]
@@ -208,6 +215,20 @@ class Lib:
 
     def seed_hit_search(self, sub, q=None, slot=-1, xdrop=910, hsp_threshold=3000, entropic=True,
                         extend=True, start=0, end=0):
+        return self._search(None, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end)
+
+    def seed_hit_search_self(self, sub, q=None, same_strand=True, band_width=0, sep1=None, sep2=None, slot=-1, xdrop=910,
+                             hsp_threshold=3000, entropic=True, extend=True, start=0, end=0):
+        """lastz --self (and --band): q is the target or its reverse complement; sep1 / sep2 the separators of a
+        [multi] sequence (partitions' sepBefore values + the final NUL), None without partitions."""
+        s = SelfArgs()
+        s.same_strand, s.band_width = int(bool(same_strand)), band_width
+        seps = [np.ascontiguousarray(x if x is not None else [], dtype=np.uint32) for x in (sep1, sep2)]
+        s.sep1, s.n_sep1 = (_ptr(seps[0]) if len(seps[0]) else None), len(seps[0])
+        s.sep2, s.n_sep2 = (_ptr(seps[1]) if len(seps[1]) else None), len(seps[1])
+        return self._search(s, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end)
+
+    def _search(self, self_args, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end):
         a = SearchArgs()
         sub = np.ascontiguousarray(sub, dtype=np.int32)
         if q is not None:
@@ -220,7 +241,11 @@ class Lib:
         a.entropic, a.extend = int(entropic), int(extend)
         out = C.c_void_p()
         n = C.c_uint64()
-        self._check(self._f("seed_hit_search")(C.byref(a), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search")
+        if self_args is None:
+            self._check(self._f("seed_hit_search")(C.byref(a), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search")
+        else:
+            self._check(self.L.lzgpu_seed_hit_search_self(C.byref(a), C.byref(self_args), C.byref(out), C.byref(n)),
+                        "lzgpu_seed_hit_search_self")
         res = np.zeros(n.value, dtype=HSP_DTYPE)
         if n.value:
             C.memmove(_ptr(res), out, n.value * HSP_DTYPE.itemsize)
