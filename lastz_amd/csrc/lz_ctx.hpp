@@ -71,6 +71,9 @@ struct LzCtx {
     LzSeedDev seed;
     DevBuf wstart, wpos;            // CSR table
     u64 num_words = 0;
+    u64 table_gen = 0;              // counts the changes of wpos (table build, adopt, commit)
+    DevBuf wctx;                    // derived, like two_x: 32 bytes of the target's 2-bit codes per table entry (lz_lut.hpp; read by k_scan_hits2)
+    u64 wctx_gen = 0; uint64_t wctx_code_key = 0;   // the table generation and the target codes wctx was built from (0: not built)
 
     // ---- queries
     std::map<int, SeqSlot> queries; // slot -> resident query; slot -1 = B2's transient slot (a host-pointer query), LZ_TEMP_SLOT_B3 - k = problem k of a B3 batch
@@ -86,7 +89,8 @@ struct LzCtx {
     u32 blk_shift = 0, blk_count = 1;
     u64* pinned = nullptr; size_t pinned_words = 0;   // host memory the device writes small results into (no staged D2H copies)
     DevBuf bins[LZ_SETS];           // the partition (high hash byte) of every hit of the chunk, written by the scan kernel (k_hist reads them)
-    DevBuf keys[LZ_SETS];                 // hit keys of a chunk, discovery order (two sets of every per-chunk buffer: the chunk pipeline)
+    DevBuf keys[LZ_SETS];                 // hit keys of a chunk, discovery order (two sets of every per-chunk buffer: the chunk pipeline); on the fused path of scan mode 0
+                                          // the chunk's tagged records instead (k_scan_hits2), and bins / summ are not allocated
     DevBuf recs[LZ_SETS], bin_base[LZ_SETS];    // hit records partitioned by the high hash bits + the 257 partition offsets; two sets:
                                     // phase B of a chunk runs while the next chunk is filled / scanned / partitioned
     DevBuf hist[LZ_SETS], hist_part[LZ_SETS];   // per-tile partition histogram and its block sums
@@ -143,5 +147,12 @@ int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n);
 int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
                   const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ[set], and the partition byte of every hit -> bins
 int lzk_partition(LzCtx& c, int set, const u64* keys, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st);
+// the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records instead of keys / summaries / partition bytes
+int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
+int lzk_fused_reserve(LzCtx& c, int set, u64 max_n);
+int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
+                   const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st);
+int lzk_hist_tagged(LzCtx& c, const u64* tagged, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);
+int lzk_partition_tagged(LzCtx& c, const u64* tagged, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st);
 int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, const u32* bin_base, u32* diag_end,
                const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);

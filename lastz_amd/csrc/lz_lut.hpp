@@ -303,6 +303,32 @@ LZ_HD u64 lz_hit_record(u64 key, u32 summ)
     const u64 payload = slow ? (u64)(diag >> 16) : (u64)(summ & 0xFFFFu);
     return (u64)pos2 | ((u64)(diag & 0xFFu) << 31) | (payload << 39) | (slow ? (1ull << 63) : 0ull);
 }
+// the record with its partition (bits 8..15 of hashedDiag) riding in the free bits 55..62: the form k_scan_hits2 stores
+// and k_hist2 / k_partition2 read; k_partition2 clears the tag when it writes the record to its partition
+#define LZ_REC_TAG(r)     ((u32)((r) >> 55) & 0xFFu)
+#define LZ_REC_UNTAG(r)   ((r) & ~(0xFFull << 55))
+LZ_HD u64 lz_hit_record_tagged(u64 key, u32 summ) { return lz_hit_record(key, summ) | ((u64)((u32)(key >> 40) & 0xFFu) << 55); }
+
+// ---- wctx: the target context of a table entry (k_scan_hits2).  Both first windows of a hit lie in the 32 bytes of the
+// plain 2-bit array that start at byte bl(pos1) -- the left window is bytes [bl, bl + 16), the right one starts at byte
+// br = bl + 15 or bl + 16 (lz_scan_fetch in seed_kernels.hip reads the same bytes from the half-overlapping blocks) --
+// and depend on pos1 alone: entry e of wctx holds those 32 bytes for pos1 = wpos[e].
+#define LZ_WCTX_BYTES 32
+struct alignas(16) LzWctx { u32 w[LZ_WCTX_BYTES / 4]; };
+LZ_HD u32 lz_wctx_first_byte(u32 pos1) { return ((pos1 - 1u + (u32)LZ_PAD2) >> 2) - 15u; }
+LZ_HD u32 lz_wctx_right_offset(u32 pos1) { return ((pos1 + (u32)LZ_PAD2) >> 2) - lz_wctx_first_byte(pos1); }     // 15 or 16
+LZ_HD LzWctx lz_wctx_make(const u8* two, u32 pos1) { LzWctx e; __builtin_memcpy(&e, two + lz_wctx_first_byte(pos1), LZ_WCTX_BYTES); return e; }
+LZ_HD void lz_wctx_windows(const LzWctx& e, u32 pos1, LzVec16& tl, LzVec16& tr)
+{
+    const bool at16 = lz_wctx_right_offset(pos1) == 16u;
+    LZ_UNROLL_ALL
+    for (int k = 0; k < 4; k++) {
+        tl.w[k] = e.w[k];
+        const u32 at15 = lz_alignbit(e.w[4 + k], e.w[3 + k], 24u);       // bytes 15 + 4k .. 18 + 4k
+        tr.w[k] = at16 ? e.w[4 + k] : at15;
+    }
+}
+
 #define LZ_REC_POS2(r)    ((u32)((r) & 0x7FFFFFFFu))
 #define LZ_REC_LOW8(r)    ((u32)((r) >> 31) & 0xFFu)
 #define LZ_REC_PAYLOAD(r) ((u32)((r) >> 39) & 0xFFFFu)

@@ -220,7 +220,7 @@ extern "C" void lzgpu_shutdown(void)
     if (c.pinned) { (void)hipHostFree(c.pinned); c.pinned = nullptr; c.pinned_words = 0; }
     DevBuf* bufs[] = { &c.target.raw, &c.target.code, &c.wstart, &c.wpos, &c.cnt, &c.off, &c.pk, &c.wiv, &c.wsk, &c.wsv, &c.lut,
                        &c.sort_tmp, &c.scan_tmp, &c.diag_end, &c.score_tab, &c.hsp_out, &c.hsp_count, &c.hsp_mc,
-                       &c.dev_counters, &c.tb_keys, &c.tb_vals, &c.tb_keys2, &c.tb_vals2 };
+                       &c.dev_counters, &c.tb_keys, &c.tb_vals, &c.tb_keys2, &c.tb_vals2, &c.wctx };
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < LZ_SETS; k++) { DevBuf* sb[] = { &c.bins[k], &c.keys[k], &c.recs[k], &c.bin_base[k], &c.hist[k], &c.hist_part[k], &c.summ[k], &c.scan_tasks[k], &c.scan_ntasks[k] }; for (DevBuf* b : sb) b->release(); }
     for (auto& kv : c.queries) { kv.second.raw.release(); kv.second.code.release(); kv.second.dp.release(); kv.second.nib.release(); kv.second.two.release(); kv.second.spc.release(); kv.second.occ_dev.release(); }
@@ -240,6 +240,7 @@ extern "C" void lzgpu_shutdown(void)
     if (c.ev_init) (void)hipEventDestroy(c.ev_init);
     c.ev_init = nullptr; c.stream2 = nullptr; c.stream3 = nullptr;
     c.stream = nullptr; c.inited = false; c.have_table = false; c.device = -1;
+    c.wctx_gen = 0; c.wctx_code_key = 0;
     c.n_owners = 1; c.owner = 0; c.last_order.clear();
 }
 
@@ -432,7 +433,7 @@ extern "C" int lzgpu_table_adopt(const lz_table_geom* g)
     LzCtx& c = g_ctx;
     if (!g) return LZGPU_ERR_ARG;
     if ((rc = lzh_seed_to_dev(&g->seed, c.seed))) return rc;
-    c.have_table = false; c.geom = *g; c.num_words = g->num_words;
+    c.have_table = false; c.geom = *g; c.num_words = g->num_words; c.table_gen++;
     size_t total = (size_t)g->tlen + 2 * LZ_SEQ_PAD + 16;
     if ((rc = c.target.raw.ensure(total))) return rc;
     if ((rc = c.target.code.ensure(total))) return rc;
@@ -467,6 +468,7 @@ extern "C" int lzgpu_table_commit(void)
         if (c.geom.tlen) LZ_HIP(hipMemcpy(c.target.host.data(), c.target.raw_base(), c.geom.tlen, hipMemcpyDeviceToHost));
         c.target.code_key = 0; c.target.dp_key = 0;
     }
+    c.table_gen++;                                              // (the caller wrote wpos)
     c.have_table = true;
     return 0;
 }
@@ -498,6 +500,32 @@ struct HostProf {
 static HostProf g_hp;
 
 // the search proper; with c.self.mode != LZ_SELF_OFF the count and fill kernels drop the hits a self-comparison drops
+
+// wctx (lz_ctx.hpp) for the table and the target codes as they are now: rebuilt when either changed since it was
+// built.  It is not to crowd out the per-chunk buffers: when it would take more than half of the device memory that
+// is free (counting what it holds already), or the allocation fails, `fused` comes back false and the search runs
+// the two kernels -- no error.
+static int lz_wctx_prepare(LzCtx& c, bool& fused)
+{
+    if (c.wctx.p && c.wctx_gen == c.table_gen && c.wctx_code_key == c.target.code_key && c.target.code_key) return 0;
+    const size_t need = (size_t)c.num_words * LZ_WCTX_BYTES;
+    if (c.num_words == 0) { fused = false; return 0; }
+    if (need > c.wctx.cap || !c.wctx.p) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || need > (fr + c.wctx.cap) / 2 || c.wctx.ensure(need) != 0) {
+            (void)hipGetLastError(); c.last_error.clear();
+            c.wctx_gen = 0; c.wctx_code_key = 0;
+            fused = false;
+            return 0;
+        }
+    }
+    c.wctx_gen = 0; c.wctx_code_key = 0;
+    int rc = lzk_wctx_build(c);
+    if (rc) return rc;
+    c.wctx_gen = c.table_gen; c.wctx_code_key = c.target.code_key;
+    return 0;
+}
+
 static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
 {
     int rc = require_init(); if (rc) return rc;
@@ -603,29 +631,6 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     if (fetch_err != hipSuccess) return lz_fail(LZGPU_ERR_HIP, "prefix fetch failed: %s", hipGetErrorString(fetch_err));
 
     g_hp.lap(2, "chunk plan");
-    u64 max_chunk = 0;
-    for (auto& ch : chunks) if (ch.nh > max_chunk) max_chunk = ch.nh;
-    // LZGPU_OVERLAP=1: the chunk pipeline over three streams (below); default: one stream, one buffer set
-    static const bool overlap = getenv("LZGPU_OVERLAP") != nullptr && getenv("LZGPU_SERIAL") == nullptr;
-    const int nsets = overlap ? (int)std::min<size_t>(chunks.size() ? chunks.size() : 1, LZ_SETS) : 1;
-    if (max_chunk) {
-        if ((rc = c.keys[0].ensure((size_t)max_chunk * 8))) return rc;
-        if ((rc = c.bins[0].ensure((size_t)max_chunk + 64))) return rc;      // k_fill_hits writes a partition byte per hit on every path (the plain-hit path included)
-        if (a->extend) {
-            const size_t ntiles = (size_t)((max_chunk + LZ_PP_TILE_HOST - 1) / LZ_PP_TILE_HOST), nblocks = (ntiles + 255) / 256;
-            for (int k = 0; k < nsets; k++) {
-                if ((rc = c.keys[k].ensure((size_t)max_chunk * 8))) return rc;
-                if ((rc = c.bins[k].ensure((size_t)max_chunk + 64))) return rc;
-                if ((rc = c.recs[k].ensure((size_t)max_chunk * 8))) return rc;
-                if ((rc = c.bin_base[k].ensure(257 * 4))) return rc;
-                if ((rc = c.hist[k].ensure(ntiles * 256 * 4))) return rc;
-                if ((rc = c.hist_part[k].ensure(nblocks * 256 * 4))) return rc;
-            }
-        }
-    }
-    const u32 out_cap = (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
-    if (a->extend && (rc = c.hsp_out.ensure((size_t)out_cap * sizeof(LzHspRec)))) return rc;
-
     LzExtendParams P;
     P.tcode = c.target.code_base(); P.tlen = c.geom.tlen;
     P.qcode = qs->code_base();      P.qlen = qlen;
@@ -660,6 +665,37 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     }
     c.last_scan_mode = mode;
 
+    u64 max_chunk = 0;
+    for (auto& ch : chunks) if (ch.nh > max_chunk) max_chunk = ch.nh;
+    // LZGPU_OVERLAP=1: the chunk pipeline over three streams (below); default: one stream, one buffer set
+    static const bool overlap = getenv("LZGPU_OVERLAP") != nullptr && getenv("LZGPU_SERIAL") == nullptr;
+    const int nsets = overlap ? (int)std::min<size_t>(chunks.size() ? chunks.size() : 1, LZ_SETS) : 1;
+    // scan mode 0 takes the fused path (k_scan_hits2: enumeration + phase A over the context-inlined table, tagged
+    // records in keys[] and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
+    // the fill variant in use is one the fused kernel does not reproduce (bucket owners, LZGPU_FILL_SHUFFLE), or
+    // wctx cannot be had (lz_wctx_prepare)
+    static const bool fused_off = getenv("LZGPU_FUSED_SCAN") != nullptr && atoi(getenv("LZGPU_FUSED_SCAN")) == 0;
+    bool fused = a->extend && mode == 0 && max_chunk && !fused_off && c.n_owners <= 1 && getenv("LZGPU_FILL_SHUFFLE") == nullptr;
+    if (fused && (rc = lz_wctx_prepare(c, fused))) return rc;
+    if (max_chunk) {
+        if ((rc = c.keys[0].ensure((size_t)max_chunk * 8))) return rc;
+        if (!fused && (rc = c.bins[0].ensure((size_t)max_chunk + 64))) return rc;      // k_fill_hits writes a partition byte per hit on every path (the plain-hit path included)
+        if (a->extend) {
+            const size_t ntiles = (size_t)((max_chunk + LZ_PP_TILE_HOST - 1) / LZ_PP_TILE_HOST), nblocks = (ntiles + 255) / 256;
+            for (int k = 0; k < nsets; k++) {
+                if ((rc = c.keys[k].ensure((size_t)max_chunk * 8))) return rc;
+                if (!fused && (rc = c.bins[k].ensure((size_t)max_chunk + 64))) return rc;
+                if ((rc = c.recs[k].ensure((size_t)max_chunk * 8))) return rc;
+                if ((rc = c.bin_base[k].ensure(257 * 4))) return rc;
+                if ((rc = c.hist[k].ensure(ntiles * 256 * 4))) return rc;
+                if ((rc = c.hist_part[k].ensure(nblocks * 256 * 4))) return rc;
+            }
+        }
+    }
+    const u32 out_cap = (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
+    if (a->extend && (rc = c.hsp_out.ensure((size_t)out_cap * sizeof(LzHspRec)))) return rc;
+
+
     std::vector<lz_hsp> plain;
     // ---- 3. per chunk, a three-stage pipeline over three streams and two sets of every per-chunk buffer:
     //   stream  (F): k_fill_hits -> k_hist + scans            keys, partition offsets           memory-bound
@@ -668,7 +704,7 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     // so that chunk c's phase B, chunk c+1's scans and chunk c+2's fill share the CUs (the scan kernel leaves
     // LDS, registers and wave slots for the others' workgroups).  Phase B launches are ordered among themselves
     // on stream2 (diagEnd carries from chunk to chunk); a buffer set is rewritten only after its last reader.
-    if (a->extend && max_chunk) for (int k = 0; k < nsets; k++) if ((rc = lzk_scan_reserve(c, k, mode, max_chunk))) return rc;
+    if (a->extend && max_chunk) for (int k = 0; k < nsets; k++) if ((rc = fused ? lzk_fused_reserve(c, k, max_chunk) : lzk_scan_reserve(c, k, mode, max_chunk))) return rc;
     LZ_HIP(hipEventRecord(c.ev_init, c.stream));              // state resets above are on stream 1
     LZ_HIP(hipStreamWaitEvent(c.stream2, c.ev_init, 0));
     LZ_HIP(hipStreamWaitEvent(c.stream3, c.ev_init, 0));
@@ -705,6 +741,23 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
         if (reuse && pending == set) { if ((rc = settle(pending))) return rc; pending = -1; }   // (fewer than three sets)
         // F: keys + histogram (every buffer of the set is free once its phase B is done)
         if (reuse) LZ_HIP(hipStreamWaitEvent(sF, c.ev_extended[set], 0));
+        if (fused) {
+            // the fused launch in the place of fill + scans (on the scans' stream, behind the set's last reader), then
+            // histogram and partition from the tagged records
+            LZ_HIP(hipEventRecord(c.ev_keys[set], sF));
+            LZ_HIP(hipStreamWaitEvent(sS, c.ev_keys[set], 0));
+            if ((rc = lzk_scan_fused(c, set, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, ch.nh, P, Q,
+                                     c.lut.as<LzLutEntry>(), c.keys[set].as<u64>(), sS))) return rc;
+            LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
+            LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
+            if ((rc = lzk_hist_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
+            if ((rc = lzk_partition_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.recs[set].as<u64>(), sB))) return rc;
+            LZ_HIP(hipEventRecord(c.ev_part[set], sB));
+            if (pending >= 0) { if ((rc = settle(pending))) return rc; }
+            pending = set;
+            ci++;
+            continue;
+        }
         if ((rc = lzk_fill_hits(c, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, c.keys[set].as<u64>(), sF))) return rc;
         LZ_HIP(hipEventRecord(c.ev_keys[set], sF));
         // S: the scans

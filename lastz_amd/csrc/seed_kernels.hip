@@ -159,6 +159,7 @@ int lzk_table_build(LzCtx& c)
     LZ_HIP(hipStreamSynchronize(c.stream));
     c.timer.resolve();
     c.num_words = nw;
+    c.table_gen++;                                       // (wctx follows wpos: lzk_wctx_build)
     if ((rc = c.wpos.ensure((size_t)(nw ? nw : 1) * 4))) return rc;
     LZ_HIP(hipMemcpyAsync(c.wpos.p, c.tb_vals2.p, (size_t)nw * 4, hipMemcpyDeviceToDevice, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
@@ -1244,6 +1245,361 @@ int lzk_partition(LzCtx& c, int set, const u64* keys, u64 n, const u32* hist, co
     static const bool ballots = getenv("LZGPU_PARTITION_BALLOTS") != nullptr;  // A/B aid: round 2's ballot-match ranks
     if (ballots) hipLaunchKernelGGL(k_partition<false>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, part, recs);
     else         hipLaunchKernelGGL(k_partition<true>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, part, recs);
+    c.timer.end(st);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The fused path of scan mode 0: hit enumeration and phase A in one kernel, over a context-inlined table.
+//   k_build_wctx   wctx[e] = the 32 bytes of the target's 2-bit array that hold both first windows of pos1 = wpos[e]
+//                  (lz_lut.hpp, lz_wctx_make): k_scan_hits gathers one random 64-byte line per hit for these; here they sit
+//                  beside the table entry and are read where k_fill_hits2 reads wpos[] -- in ascending runs, one per list.
+//   k_scan_hits2   k_fill_hits2's steps 1-2 (the same code), then per hit: wpos[e] + wctx[e] + the query windows (which depend
+//                  on pos2 alone: one line per entry), lz_scan_round<false>, ONE tagged 8-byte record at the hit's place in
+//                  discovery order.  No keys, no summaries, no partition bytes.  Persistent waves (the 64 KiB tables are
+//                  loaded once per workgroup) that stride over the 64-entry groups of the sorted list.
+//   k_scan_tasks2  replaces the provisional record a queued hit left (payload and SLOW flag were missing).
+//   k_hist2 / k_partition2   read the tagged records (the partition rides in bits 55..62).
+__global__ void __launch_bounds__(LZ_TPB)
+k_build_wctx(const u32* __restrict__ wpos, u64 num_words, const u8* __restrict__ two, LzVec16* __restrict__ wctx)
+{
+    const u64 j = (u64)blockIdx.x * LZ_TPB + threadIdx.x;       // one 16-byte half of an entry per lane
+    if (j >= 2 * num_words) return;
+    const u32 pos1 = wpos[j >> 1];
+    wctx[j] = lz_load16(two + lz_wctx_first_byte(pos1) + 16u * (u32)(j & 1u));
+}
+
+template <int CAP> struct LzFuse2Wave {
+    alignas(16) u32 own32[CAP / 2];                  // as LzFill2Wave
+    u32 lsrc[64 * LZ_FILL_GROUP];
+    uint2 ent[64];
+};
+// the loads of one trip of 64 hits (issued a trip ahead of the arithmetic)
+struct LzFuseTrip { u32 p1, pos2, dst; bool ok; LzWctx cx; LzVec16 ql, qr; };
+
+template <bool SELF, int TPB, int CAP>
+__global__ void __launch_bounds__(TPB)
+k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
+             const u32* __restrict__ wstart, const u32* __restrict__ wpos, const LzWctx* __restrict__ wctx,
+             const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, const u64* __restrict__ off, u64 base,
+             LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut_g,
+             u64* __restrict__ recs, LzScanTask* __restrict__ tasks, u32* __restrict__ n_tasks, u32 region_cap, LzSelfDev self)
+{
+    static_assert(CAP % 512 == 0, "whole 16-byte groups of own[] per lane");
+    constexpr int WORDS = CAP / 2 / 64;
+    __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
+    __shared__ LzFuse2Wave<CAP> shw[TPB / 64];
+    for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += TPB) lut[k] = lut_g[k];
+    __syncthreads();
+    LzFuse2Wave<CAP>& sh = shw[threadIdx.x >> 6];
+    unsigned short* const own = reinterpret_cast<unsigned short*>(sh.own32);
+    const u32 lane = threadIdx.x & 63u;
+    const u32 region = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), nwaves = gridDim.x * (TPB / 64);
+    LzScanTask* const my_tasks = tasks + (size_t)region * region_cap;
+    u32 my_n = 0;
+    const u32 ngroups = (n + 63u) / 64u;
+    for (u32 grp = region; grp < ngroups; grp += nwaves) {      // wave-uniform
+        const u32 j = grp * 64u + lane;                         // one sorted entry per lane
+        u32 w_l = 0, i_l = 0; bool in = false;
+        if (j < n) { w_l = sk[j] & ((2u << sd.weight) - 1u); i_l = sv[j]; in = !(w_l >> sd.weight) && i_l >= i0 && i_l < i1; }
+        if (!__ballot(in)) continue;
+        const u32 dbase = in ? (u32)(off[i_l] - base) : 0u;
+        const u32 pos2 = lo + i_l + 1u;
+        u32 slo = 0, shi = 0;
+        if (SELF) lz_self_bounds(self, pos2, slo, shi);
+        u32 carry = 0;
+        for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {
+            // ---- 1. bounds of the lane's lists (k_fill_hits2)
+            u32 la[LZ_FILL_GROUP], len[LZ_FILL_GROUP]; u32 total = 0;
+#pragma unroll
+            for (int p = 0; p < LZ_FILL_GROUP; p++) {
+                const bool on = in && r + p < sd.nprobes;
+                const u32 w = on ? (w_l ^ sd.probe_xor[(r + p) & (LZ_MAX_PROBES - 1)]) : 0u;
+                la[p] = wstart[w]; len[p] = wstart[w + 1];
+            }
+#pragma unroll
+            for (int p = 0; p < LZ_FILL_GROUP; p++) {
+                const bool on = in && r + p < sd.nprobes;
+                len[p] = on ? len[p] - la[p] : 0u;
+                if (!SELF) total += len[p];
+            }
+            if (SELF) {
+                lz_clip_runs<LZ_FILL_GROUP>(wpos, la, len, slo, shi);
+#pragma unroll
+                for (int p = 0; p < LZ_FILL_GROUP; p++) total += len[p];
+            }
+            u32 inc = total;
+            LZ_WAVE_SCAN_U32(inc, total, lz_uadd)
+            const u32 E = inc - total;
+            const u32 T = (u32)__builtin_amdgcn_readlane((int)inc, 63);
+            {
+                u32 S = E;
+#pragma unroll
+                for (int p = 0; p < LZ_FILL_GROUP; p++) { sh.lsrc[lane * LZ_FILL_GROUP + p] = la[p] - S; S += len[p]; }
+            }
+            sh.ent[lane] = make_uint2(dbase + carry - E, pos2);
+            // ---- 2. + 3., a piece of CAP hits at a time
+            for (u32 cs = 0; cs < T; cs += CAP) {                // uniform
+                const u32 tc = (T - cs < (u32)CAP) ? T - cs : (u32)CAP;
+                uint4* const mine = reinterpret_cast<uint4*>(sh.own32 + lane * WORDS);
+#pragma unroll
+                for (int k = 0; k < WORDS / 4; k++) mine[k] = make_uint4(0u, 0u, 0u, 0u);
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+                {
+                    u32 S = E;
+#pragma unroll
+                    for (int p = 0; p < LZ_FILL_GROUP; p++) {
+                        const u32 l = len[p];
+                        if (l && S < cs + tc && S + l > cs) own[(S > cs ? S : cs) - cs] = (unsigned short)(1u + lane * LZ_FILL_GROUP + (u32)p);
+                        S += l;
+                    }
+                }
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+                u32 wv[WORDS];
+#pragma unroll
+                for (int k = 0; k < WORDS / 4; k++) { const uint4 v = mine[k]; wv[4 * k] = v.x; wv[4 * k + 1] = v.y; wv[4 * k + 2] = v.z; wv[4 * k + 3] = v.w; }
+                u32 segmax = 0;
+#pragma unroll
+                for (int k = 0; k < WORDS; k++) { const u32 m2 = lz_umax(wv[k] & 0xFFFFu, wv[k] >> 16); segmax = lz_umax(segmax, m2); }
+                u32 sinc = segmax;
+                LZ_WAVE_SCAN_U32(sinc, segmax, lz_umax)
+                u32 run = lz_dpp_u32<0x138, 0xf, 0xf>(0u, sinc);
+#pragma unroll
+                for (int k = 0; k < WORDS; k++) {
+                    const u32 a0 = lz_umax(wv[k] & 0xFFFFu, run), a1 = lz_umax(wv[k] >> 16, a0);
+                    wv[k] = a0 | (a1 << 16); run = a1;
+                }
+#pragma unroll
+                for (int k = 0; k < WORDS / 4; k++) mine[k] = make_uint4(wv[4 * k], wv[4 * k + 1], wv[4 * k + 2], wv[4 * k + 3]);
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+                // ---- 3. the hits of the piece, 64 per trip: table entry + context + query windows -> both scans' first
+                // windows -> the tagged record.  Two register sets take turns: a trip's loads are issued before the
+                // arithmetic of the trip before it.  (A lane beyond the end of the piece loads the last hit again.)
+                auto load_trip = [&](u32 tb, LzFuseTrip& t) {
+                    const u32 t0 = tb + lane;
+                    t.ok = t0 < tc;
+                    const u32 tt = t.ok ? t0 : tc - 1u;
+                    const u32 list = (u32)own[tt] - 1u;
+                    const u32 ls = sh.lsrc[list];
+                    const uint2 en = sh.ent[list / LZ_FILL_GROUP];
+                    const u32 tabs = cs + tt, e = ls + tabs;
+                    t.p1 = wpos[e]; t.cx = wctx[e];
+                    t.pos2 = en.y; t.dst = en.x + tabs;
+                    const u32 sql = en.y - 1u + (u32)LZ_PAD2;     // (lz_scan_fetch: stl - diag, str - diag)
+                    t.ql = lz_load16(Q.q2 + ((sql >> 2) - 15u)); t.qr = lz_load16(Q.q2 + ((sql + 1u) >> 2));
+                };
+                auto scan_trip = [&](const LzFuseTrip& t) {
+                    const u64 key = lz_hit_key(t.p1, t.pos2);
+                    LzLutRaw<false> rl, rr;
+                    lz_wctx_windows(t.cx, t.p1, rl.tv, rr.tv);
+                    rl.qv = t.ql; rr.qv = t.qr;
+                    u32 summ;
+                    lz_scan_round<false>(P, Q, lut, nullptr, key, t.ok, rl, rr, t.dst, lane, summ, my_tasks, my_n, region_cap);
+                    // (a queued hit: summ == 0, the provisional record k_scan_tasks2 completes)
+                    if (t.ok) LZ_NT_ST(lz_hit_record_tagged(key, summ), recs + t.dst);
+                };
+                LzFuseTrip ta, tb2;
+                load_trip(0u, ta);
+#pragma unroll 1
+                for (u32 tb = 0;;) {                             // uniform
+                    if (tb + 64u < tc) load_trip(tb + 64u, tb2);
+                    scan_trip(ta);
+                    tb += 64u; if (tb >= tc) break;
+                    if (tb + 64u < tc) load_trip(tb + 64u, ta);
+                    scan_trip(tb2);
+                    tb += 64u; if (tb >= tc) break;
+                }
+                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+            }
+            carry += total;
+        }
+    }
+    if (lane == 0) n_tasks[region] = my_n < region_cap ? my_n : region_cap;
+}
+
+__global__ void __launch_bounds__(LZ_ST_TPB)
+k_scan_tasks2(LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut_g, const LzScanTask* __restrict__ tasks,
+              const u32* __restrict__ n_tasks, u32 n_regions, u32 region_cap, u64* __restrict__ recs)
+{
+    __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
+    for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += LZ_ST_TPB) lut[k] = lut_g[k];
+    __syncthreads();
+    for (u32 region = blockIdx.x; region < n_regions; region += gridDim.x) {
+        const u32 nt = n_tasks[region];
+        for (u32 k = threadIdx.x; k < nt; k += (u32)LZ_ST_TPB) {
+            const LzScanTask t = tasks[(size_t)region * region_cap + k];
+            LzLutScan L = t.L, R = t.R;
+            // the hit's pos1 from the task (reading the provisional record back would fetch a line for 8 bytes): a side that goes on
+            // (and a task has one) has moved LZ_LUT_WIN_B bases per window it ran -- without special bytes a scan goes on in no other way
+            const u32 pos1 = L.alive == 1 ? L.s + (u32)LZ_LUT_WIN_B * L.nwin : R.s - (u32)LZ_LUT_WIN_B * R.nwin;
+            while (L.alive == 1 && L.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<false, false>(Q, lut, t.diag, L, nullptr);
+            while (R.alive == 1 && R.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<true, false>(Q, lut, t.diag, R, nullptr);
+            recs[t.idx] = lz_hit_record_tagged(lz_hit_key(pos1, pos1 - (u32)t.diag), lz_lut_summary(L, R, P.min_score));
+        }
+    }
+}
+
+__global__ void __launch_bounds__(LZ_TPB)
+k_hist2(const u64* __restrict__ tagged, u64 n, u32* __restrict__ hist)
+{
+    __shared__ u32 cnt[LZ_NBIN];
+    cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const u64 base = (u64)blockIdx.x * LZ_PP_TILE;
+    typedef u64 lz_u64x2 __attribute__((ext_vector_type(2)));
+#pragma unroll 4
+    for (int r = 0; r < LZ_PP_TILE / (LZ_TPB * 2); r++) {       // two records per lane and step
+        const u64 i = base + ((u64)r * LZ_TPB + threadIdx.x) * 2u;
+        if (i + 1u < n) {
+            const lz_u64x2 v = *reinterpret_cast<const lz_u64x2*>(tagged + i);
+            atomicAdd(&cnt[LZ_REC_TAG(v.x)], 1u); atomicAdd(&cnt[LZ_REC_TAG(v.y)], 1u);
+        } else if (i < n) atomicAdd(&cnt[LZ_REC_TAG(tagged[i])], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)blockIdx.x * LZ_NBIN + threadIdx.x] = cnt[threadIdx.x];
+}
+
+// k_partition<true> on tagged records
+__global__ void __launch_bounds__(LZ_PP_TPB)
+k_partition2(const u64* __restrict__ tagged, u64 n, const u32* __restrict__ hist, const u32* __restrict__ part, u64* __restrict__ recs)
+{
+    __shared__ LzPartShared sh;
+    const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    const u32 tile = blockIdx.x;
+    const u64 base = (u64)tile * LZ_PP_TILE;
+    const u32 tile_n = (n - base < (u64)LZ_PP_TILE) ? (u32)(n - base) : (u32)LZ_PP_TILE;
+    for (u32 k = tid; k < LZ_PP_WAVES * LZ_NBIN; k += LZ_PP_TPB) { (&sh.wcnt[0][0])[k] = 0; (&sh.bm[0][0])[k] = 0ull; }
+    const u32 l0 = w * (64u * LZ_PP_ROUNDS) + lane;
+    u64 rr[LZ_PP_ROUNDS];
+#pragma unroll
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) rr[r] = (l0 + 64u * r < tile_n) ? tagged[base + l0 + 64u * r] : 0ull;
+    __syncthreads();
+    u32 slot[LZ_PP_ROUNDS];
+#pragma unroll
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
+        const bool valid = l0 + 64u * r < tile_n;
+        const u32 bin = LZ_REC_TAG(rr[r]);
+        if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);
+        const u64 peers = valid ? sh.bm[w][bin] : 0ull;
+        const u32 old = valid ? sh.wcnt[w][bin] : 0u;
+        if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }
+        slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));
+    }
+    __syncthreads();
+    u32 tot = 0;
+    if (tid < LZ_NBIN) {
+        for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }
+        sh.gbase[tid] = part[(size_t)(tile >> 8) * LZ_NBIN + tid] + hist[(size_t)tile * LZ_NBIN + tid];
+    }
+    const u32 ts = lz_exscan256(tot, sh.wtot);
+    if (tid < LZ_NBIN) sh.tstart[tid] = ts;
+    if (tid == 0) sh.tstart[LZ_NBIN] = tile_n;
+    __syncthreads();
+#pragma unroll
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
+        const u32 bin = LZ_REC_TAG(rr[r]);
+        if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = rr[r];
+    }
+    __syncthreads();
+    for (u32 k = tid; k < tile_n; k += LZ_PP_TPB) {
+        const u64 r = sh.stage[k];
+        const u32 b = LZ_REC_TAG(r);
+        recs[(size_t)sh.gbase[b] + (k - sh.tstart[b])] = LZ_REC_UNTAG(r);
+    }
+}
+
+int lzk_wctx_build(LzCtx& c)
+{
+    const u64 nw = c.num_words;
+    if (nw == 0) return 0;
+    c.timer.begin("k_build_wctx", c.stream);
+    hipLaunchKernelGGL(k_build_wctx, dim3((unsigned)((2 * nw + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, c.stream,
+                       c.wpos.as<u32>(), nw, c.target.two.as<u8>(), c.wctx.as<LzVec16>());
+    c.timer.end(c.stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+
+// the fused kernel's grid (one workgroup per CU: its LDS) and the task regions of its waves
+// LDS: the tables + a wave's own[] of CAP cells and 4.5 KiB of lists: 8 waves x 2560 cells, 12 x 1024 or 16 x 512 in 160 KiB.
+// The kernel is bound by the latency of the scans' dependent table look-ups, which only other waves hide: 84.5, 67.9, 61.6 ms per
+// step on the 50 Mbp pair with 8, 12, 16 waves (121 VGPRs: four waves per SIMD), however short the pieces get.  A
+// self-comparison's clipping needs 177 registers: it runs with 8 waves.
+static u32 lz_fused_tpb(LzCtx& c)
+{
+    static const int env = getenv("LZGPU_FUSE_TPB") ? atoi(getenv("LZGPU_FUSE_TPB")) : 0;  // A/B aid: 512, 768 or 1024
+    if (c.self.mode != LZ_SELF_OFF) return 512u;
+    return (env == 512 || env == 768 || env == 1024) ? (u32)env : 1024u;
+}
+static void lz_fused_geometry(LzCtx& c, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
+{
+    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
+    grid = (u32)cus; n_regions = grid * (lz_fused_tpb(c) / 64u);
+    region_cap = (u32)std::min<u64>(n_hits / 32 / n_regions + 64, 1u << 20);
+    static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook (lz_scan_geometry)
+    if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
+}
+int lzk_fused_reserve(LzCtx& c, int set, u64 max_n)
+{
+    u32 grid, n_regions, region_cap; int rc;
+    lz_fused_geometry(c, max_n, grid, n_regions, region_cap);
+    if ((rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
+    return c.scan_ntasks[set].ensure((size_t)n_regions * 4);
+}
+// lzk_fill_hits + lzk_scan_hits of mode 0 in one launch: the chunk's hits as tagged records, in discovery order
+int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
+                   const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st)
+{
+    if (n == 0 || i1 <= i0 || n_hits == 0) return 0;
+    if (!c.blk_start_host.empty()) {                            // (lzk_fill_hits: the chunk's range of the sorted list)
+        const u32 b0 = i0 >> c.blk_shift, b1 = (i1 - 1) >> c.blk_shift;
+        const u64 j0 = c.blk_start_host[b0], j1 = c.blk_start_host[std::min<u32>(b1 + 1, c.blk_count)];
+        sk += j0; sv += j0; n = (u32)(j1 - j0);
+        if (n == 0) return 0;
+    }
+    int rc;
+    u32 grid, n_regions, region_cap;
+    lz_fused_geometry(c, n_hits, grid, n_regions, region_cap);
+    if ((rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
+    if ((rc = c.scan_ntasks[set].ensure((size_t)n_regions * 4))) return rc;
+    LzScanTask* tasks = c.scan_tasks[set].as<LzScanTask>(); u32* ntk = c.scan_ntasks[set].as<u32>();
+    c.timer.begin("k_scan_hits", st);
+    const u32 tpb = lz_fused_tpb(c);
+#define LZ_FUSED_LAUNCH(S_, T_, C_, self_) hipLaunchKernelGGL((k_scan_hits2<S_, T_, C_>), dim3(grid), dim3(T_), 0, st, lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), \
+                           c.wctx.as<LzWctx>(), sk, sv, n, off, base, P, Q, lut, tagged, tasks, ntk, region_cap, self_)
+    if (c.self.mode != LZ_SELF_OFF) LZ_FUSED_LAUNCH(true, 512, 2560, c.self);
+    else if (tpb == 512)            LZ_FUSED_LAUNCH(false, 512, 2560, LzSelfDev{});
+    else if (tpb == 768)            LZ_FUSED_LAUNCH(false, 768, 1024, LzSelfDev{});
+    else                            LZ_FUSED_LAUNCH(false, 1024, 512, LzSelfDev{});
+#undef LZ_FUSED_LAUNCH
+    c.timer.end(st);
+    LZ_HIP(hipGetLastError());
+    c.timer.begin("k_scan_tasks", st);
+    hipLaunchKernelGGL(k_scan_tasks2, dim3(std::min<u32>(n_regions, 4u * grid)), dim3(LZ_ST_TPB), 0, st, P, Q, lut, tasks, ntk, n_regions, region_cap, tagged);
+    c.timer.end(st);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int lzk_hist_tagged(LzCtx& c, const u64* tagged, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st)
+{
+    const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE), nblocks = (ntiles + 255u) / 256u;
+    c.timer.begin("k_hist", st);
+    hipLaunchKernelGGL(k_hist2, dim3(ntiles), dim3(LZ_TPB), 0, st, tagged, n, hist);
+    c.timer.end(st);
+    c.timer.begin("k_hist_scan", st);
+    hipLaunchKernelGGL(k_hist_scan1, dim3(nblocks), dim3(LZ_NBIN), 0, st, hist, ntiles, part);
+    hipLaunchKernelGGL(k_hist_scan2, dim3(1), dim3(LZ_NBIN), 0, st, part, nblocks, bin_base);
+    c.timer.end(st);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+int lzk_partition_tagged(LzCtx& c, const u64* tagged, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st)
+{
+    if (n == 0) return 0;
+    const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
+    c.timer.begin("k_partition", st);
+    hipLaunchKernelGGL(k_partition2, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, tagged, n, hist, part, recs);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;
