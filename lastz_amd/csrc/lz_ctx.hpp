@@ -88,12 +88,12 @@ struct LzCtx {
     std::vector<u64> blk_start_host;
     u32 blk_shift = 0, blk_count = 1;
     u64* pinned = nullptr; size_t pinned_words = 0;   // host memory the device writes small results into (no staged D2H copies)
-    DevBuf bins[LZ_SETS];           // the partition (high hash byte) of every hit of the chunk, written by the scan kernel (k_hist reads them)
+    DevBuf bins[LZ_SETS];           // the partition (high hash byte) of every hit of the chunk, written by the scan kernels of the unfused path
     DevBuf keys[LZ_SETS];                 // hit keys of a chunk, discovery order (two sets of every per-chunk buffer: the chunk pipeline); on the fused path of scan mode 0
-                                          // the chunk's tagged records instead (k_scan_hits2), and bins / summ are not allocated
-    DevBuf recs[LZ_SETS], bin_base[LZ_SETS];    // hit records partitioned by the high hash bits + the 257 partition offsets; two sets:
-                                    // phase B of a chunk runs while the next chunk is filled / scanned / partitioned
-    DevBuf hist[LZ_SETS], hist_part[LZ_SETS];   // per-tile partition histogram and its block sums
+                                          // the chunk's tagged records instead (k_scan_hits2), and bins / summ are not allocated.  The partition kernels
+                                          // turn it in place into the chunk's records, every tile sorted by partition (lz_tile_runs.hpp): 8 bytes per hit
+    DevBuf bin_base[LZ_SETS];             // the 257 partition offsets (ranks); sets: phase B of a chunk runs while the next chunk is scanned / partitioned
+    DevBuf hist[LZ_SETS], hist_part[LZ_SETS], run_addr[LZ_SETS];   // [tile][partition]: records, then first rank inside the block of 256 tiles; the blocks' first ranks; where the run lies
     DevBuf summ[LZ_SETS], scan_tasks[LZ_SETS], scan_ntasks[LZ_SETS];   // phase A: 4-byte summary per hit of the chunk; the scans that go on past their first window
     DevBuf lut;                     // phase-A tables (lz_lut.hpp)
     DevBuf sort_tmp, scan_tmp;
@@ -137,22 +137,19 @@ int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv
 int lzk_hsp_match_counts(LzCtx& c, const LzHspRec* recs, const u32* n_rec_dev, u32 cap, u32 launch_for,
                          const u8* traw, const u8* qraw, const u8* tcode, const u8* qcode, u32* counts, hipStream_t s);
 struct LzLutParams; struct LzLutEntry;
-#ifndef LZ_PP_TILE_HOST
-#define LZ_PP_TILE_HOST 16384       // hits per tile of k_hist / k_partition (sizes the partition histogram); 8192 with 512 lanes: 24.5 ms per step, 16384 with 1024: 21.7
-#endif
+#include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
 int lzk_pack2(LzCtx& c, const u8* code_base, const u8* raw_base, u32 len, u8* two, u8* spc, u32 nmask, u32* flags256);
 int lzk_overlap32(LzCtx& c, const u8* src, u8* dst, size_t nblocks);
-int lzk_hist(LzCtx& c, const u8* bins, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);
+int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);      // after the partition of the chunk
 int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n);
 int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
                   const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ[set], and the partition byte of every hit -> bins
-int lzk_partition(LzCtx& c, int set, const u64* keys, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st);
+int lzk_partition(LzCtx& c, int set, u64* keys, u64 n, u32* hist, u32* run_addr, hipStream_t st);        // keys -> records, in place
 // the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records instead of keys / summaries / partition bytes
 int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
 int lzk_fused_reserve(LzCtx& c, int set, u64 max_n);
 int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
                    const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st);
-int lzk_hist_tagged(LzCtx& c, const u64* tagged, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);
-int lzk_partition_tagged(LzCtx& c, const u64* tagged, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st);
-int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, const u32* bin_base, u32* diag_end,
-               const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);
+int lzk_partition_tagged(LzCtx& c, u64* tagged, u64 n, u32* hist, u32* run_addr, hipStream_t st);         // tagged records -> records, in place
+int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, u64 n, const u32* hist, const u32* hist_part, const u32* run_addr,
+               const u32* bin_base, u32* diag_end, const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);

@@ -222,7 +222,7 @@ extern "C" void lzgpu_shutdown(void)
                        &c.sort_tmp, &c.scan_tmp, &c.diag_end, &c.score_tab, &c.hsp_out, &c.hsp_count, &c.hsp_mc,
                        &c.dev_counters, &c.tb_keys, &c.tb_vals, &c.tb_keys2, &c.tb_vals2, &c.wctx };
     for (DevBuf* b : bufs) b->release();
-    for (int k = 0; k < LZ_SETS; k++) { DevBuf* sb[] = { &c.bins[k], &c.keys[k], &c.recs[k], &c.bin_base[k], &c.hist[k], &c.hist_part[k], &c.summ[k], &c.scan_tasks[k], &c.scan_ntasks[k] }; for (DevBuf* b : sb) b->release(); }
+    for (int k = 0; k < LZ_SETS; k++) { DevBuf* sb[] = { &c.bins[k], &c.keys[k], &c.bin_base[k], &c.hist[k], &c.hist_part[k], &c.run_addr[k], &c.summ[k], &c.scan_tasks[k], &c.scan_ntasks[k] }; for (DevBuf* b : sb) b->release(); }
     for (auto& kv : c.queries) { kv.second.raw.release(); kv.second.code.release(); kv.second.dp.release(); kv.second.nib.release(); kv.second.two.release(); kv.second.spc.release(); kv.second.occ_dev.release(); }
     c.target.dp.release(); c.target.nib.release(); c.target.two.release(); c.target.spc.release(); c.target.occ_dev.release();
     c.target.two_x.release(); c.target.spc_x.release();
@@ -685,10 +685,10 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
             for (int k = 0; k < nsets; k++) {
                 if ((rc = c.keys[k].ensure((size_t)max_chunk * 8))) return rc;
                 if (!fused && (rc = c.bins[k].ensure((size_t)max_chunk + 64))) return rc;
-                if ((rc = c.recs[k].ensure((size_t)max_chunk * 8))) return rc;
                 if ((rc = c.bin_base[k].ensure(257 * 4))) return rc;
                 if ((rc = c.hist[k].ensure(ntiles * 256 * 4))) return rc;
                 if ((rc = c.hist_part[k].ensure(nblocks * 256 * 4))) return rc;
+                if ((rc = c.run_addr[k].ensure(ntiles * 256 * 4))) return rc;
             }
         }
     }
@@ -698,9 +698,9 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
 
     std::vector<lz_hsp> plain;
     // ---- 3. per chunk, a three-stage pipeline over three streams and two sets of every per-chunk buffer:
-    //   stream  (F): k_fill_hits -> k_hist + scans            keys, partition offsets           memory-bound
+    //   stream  (F): k_fill_hits                              keys                              memory-bound
     //   stream3 (S): k_scan_hits -> k_scan_tasks              phase A, the 4-byte summaries     VALU-bound
-    //   stream2 (B): k_partition -> k_settle                  records in partitions, phase B    latency-bound
+    //   stream2 (B): k_partition -> k_hist_scan -> k_settle   tiles sorted in place, phase B    latency-bound
     // so that chunk c's phase B, chunk c+1's scans and chunk c+2's fill share the CUs (the scan kernel leaves
     // LDS, registers and wave slots for the others' workgroups).  Phase B launches are ordered among themselves
     // on stream2 (diagEnd carries from chunk to chunk); a buffer set is rewritten only after its last reader.
@@ -718,9 +718,10 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     hipStream_t sF = c.stream, sS = serial ? c.stream : c.stream3, sB = serial ? c.stream : c.stream2;
     // phase B needs whole CUs (128 VGPRs x 1024 lanes) and cannot share one with the scan kernel: it runs on the
     // scans' stream, behind the NEXT chunk's scans, by which time its partition (which does overlap them) is done
+    u64 set_n[LZ_SETS] = {};                                    // hits of the chunk a set holds
     auto settle = [&](int set) -> int {
         LZ_HIP(hipStreamWaitEvent(sS, c.ev_part[set], 0));
-        int r = lzk_settle(c, P, c.recs[set].as<u64>(), c.bin_base[set].as<u32>(), c.diag_end.as<u32>(), c.score_tab.as<s32>(),
+        int r = lzk_settle(c, P, c.keys[set].as<u64>(), set_n[set], c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.run_addr[set].as<u32>(), c.bin_base[set].as<u32>(), c.diag_end.as<u32>(), c.score_tab.as<s32>(),
                            c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap, d_counters, sS);
         if (r) return r;
         LZ_HIP(hipEventRecord(c.ev_extended[set], sS));
@@ -739,19 +740,20 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
         }
         const bool reuse = ci >= (size_t)nsets;                 // the set has been through the pipeline before
         if (reuse && pending == set) { if ((rc = settle(pending))) return rc; pending = -1; }   // (fewer than three sets)
-        // F: keys + histogram (every buffer of the set is free once its phase B is done)
+        // F: keys (every buffer of the set is free once its phase B is done)
         if (reuse) LZ_HIP(hipStreamWaitEvent(sF, c.ev_extended[set], 0));
         if (fused) {
             // the fused launch in the place of fill + scans (on the scans' stream, behind the set's last reader), then
-            // histogram and partition from the tagged records
+            // the tagged records sorted tile by tile where they lie, and the runs' ranks from the counts that leaves
             LZ_HIP(hipEventRecord(c.ev_keys[set], sF));
             LZ_HIP(hipStreamWaitEvent(sS, c.ev_keys[set], 0));
             if ((rc = lzk_scan_fused(c, set, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, ch.nh, P, Q,
                                      c.lut.as<LzLutEntry>(), c.keys[set].as<u64>(), sS))) return rc;
             LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
             LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-            if ((rc = lzk_hist_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
-            if ((rc = lzk_partition_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.recs[set].as<u64>(), sB))) return rc;
+            if ((rc = lzk_partition_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
+            if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
+            set_n[set] = ch.nh;
             LZ_HIP(hipEventRecord(c.ev_part[set], sB));
             if (pending >= 0) { if ((rc = settle(pending))) return rc; }
             pending = set;
@@ -766,9 +768,9 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
         LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
         // B: the partition
         LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-        // (the tile histograms from the partition bytes the scan kernel left)
-        if ((rc = lzk_hist(c, c.bins[set].as<u8>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
-        if ((rc = lzk_partition(c, set, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.recs[set].as<u64>(), sB))) return rc;
+        if ((rc = lzk_partition(c, set, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
+        if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
+        set_n[set] = ch.nh;
         LZ_HIP(hipEventRecord(c.ev_part[set], sB));
         // S again: phase B of the previous chunk (diagEnd carries from chunk to chunk: chunk order)
         if (pending >= 0) { if ((rc = settle(pending))) return rc; }

@@ -17,6 +17,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include "lz_ctx.hpp"
 #include "lz_lut.hpp"
+#include "lz_tile_runs.hpp"
 #include "lz_coop.hpp"
 
 #define LZ_TPB 256
@@ -746,10 +747,10 @@ int lzk_pack2(LzCtx& c, const u8* code_base, const u8* raw_base, u32 len, u8* tw
 // ------------------------------------------------------------------------------------------
 // B2 step 3: the hits of a chunk, which k_fill_hits wrote in discovery order, are (a) scanned independently of
 // the diagonal hash (phase A) and (b) stably partitioned by the high 8 bits of hashedDiag into 256 streams of
-// 8-byte records (lz_lut.hpp), one stream per workgroup of phase B.  One pass over the keys for the partition
-// offsets (k_hist + two small scans, on the partition bytes k_fill_hits left), one that scans (k_scan_hits,
-// k_scan_tasks), one that scatters (k_partition): 8 B + 4 B read and 8 B written per hit, where a radix sort of
-// (key, summary) pairs moved 56.
+// 8-byte records (lz_lut.hpp), one stream per workgroup of phase B.  One pass that scans (k_scan_hits,
+// k_scan_tasks) and one that sorts every tile of 16384 hits by partition where it lies (k_partition: 8 B + 4 B read
+// and 8 B written per hit in whole tiles, where a radix sort of (key, summary) pairs moved 56); two small scans over
+// the tiles' counts (k_hist_scan) give every run its rank, and phase B gathers a partition's runs (lz_tile_runs.hpp).
 // -DLZ_PHASE_CLOCKS: per-phase shader-clock totals of the phase kernels (lane 0 of every workgroup adds
 // its s_memtime deltas to a device array the host prints at shutdown); off in the product build
 #if defined(LZ_PHASE_CLOCKS)
@@ -791,30 +792,11 @@ void lz_phase_clocks_print() {}
 #ifndef LZ_PP_ROUNDS
 #define LZ_PP_ROUNDS (LZ_PP_TILE_HOST / LZ_PP_TPB)   // k_partition: records per lane
 #endif
-#define LZ_PP_TILE   (LZ_PP_TPB * LZ_PP_ROUNDS)      // hits per tile of k_hist / k_partition
+#define LZ_PP_TILE   (LZ_PP_TPB * LZ_PP_ROUNDS)      // hits per tile of k_partition
 #define LZ_PP_QCAP   96                              // unfinished scans a tile can queue (beyond that the hit is left to phase B)
 #define LZ_NBIN      256
 
-// hist[tile][bin]: hits of the tile per partition
-__global__ void __launch_bounds__(LZ_TPB)
-k_hist(const u8* __restrict__ bins, u64 n, u32* __restrict__ hist)
-{
-    __shared__ u32 cnt[LZ_NBIN];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const u64 base = (u64)blockIdx.x * LZ_PP_TILE;
-#pragma unroll
-    for (int r = 0; r < LZ_PP_TILE / (LZ_TPB * 16); r++) {      // 16 partition bytes per lane and step
-        const u64 i = base + ((u64)r * LZ_TPB + threadIdx.x) * 16u;
-        if (i < n) {
-            const LzVec16 v = lz_load16(bins + i);
-#pragma unroll
-            for (int k = 0; k < 16; k++) if (i + (u64)k < n) atomicAdd(&cnt[LZ_VBYTE(v, k)], 1u);
-        }
-    }
-    __syncthreads();
-    hist[(size_t)blockIdx.x * LZ_NBIN + threadIdx.x] = cnt[threadIdx.x];
-}
+// hist[tile][bin]: hits of the tile per partition, written by the partition kernels (lz_tile_runs.hpp)
 // per block of 256 tiles: exclusive prefix down each column, column sums to part[block][bin]
 __global__ void __launch_bounds__(LZ_NBIN)
 k_hist_scan1(u32* __restrict__ hist, u32 ntiles, u32* __restrict__ part)
@@ -840,14 +822,13 @@ k_hist_scan2(u32* __restrict__ part, u32 nblocks, u32* __restrict__ bin_base)
     for (u32 b = 0; b < nblocks; b++) part[(size_t)b * LZ_NBIN + threadIdx.x] += bb;
 }
 
-int lzk_hist(LzCtx& c, const u8* bins, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st)
+// after the partition: hist[tile][bin] -> rank of the run's first record inside its block of 256 tiles, part[block][bin] ->
+// the block's first rank, bin_base[0..256]
+int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st)
 {
     const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE), nblocks = (ntiles + 255u) / 256u;
-    c.timer.begin("k_hist", st);
-    hipLaunchKernelGGL(k_hist, dim3(ntiles), dim3(LZ_TPB), 0, st, bins, n, hist);
-    c.timer.end(st);
     c.timer.begin("k_hist_scan", st);
-    hipLaunchKernelGGL(k_hist_scan1, dim3(nblocks), dim3(LZ_NBIN), 0, st, hist, ntiles, part);
+    if (nblocks) hipLaunchKernelGGL(k_hist_scan1, dim3(nblocks), dim3(LZ_NBIN), 0, st, hist, ntiles, part);
     hipLaunchKernelGGL(k_hist_scan2, dim3(1), dim3(LZ_NBIN), 0, st, part, nblocks, bin_base);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
@@ -891,7 +872,7 @@ __device__ __forceinline__ u32 lz_exscan256(u32 v, u32* wtot /*LDS, [4]*/)
 //                 this code all the time.  Output: the 4-byte summary of a hit whose scans both ended; the rare hit
 //                 with a scan that goes on (~3 %) becomes a 64-byte task in a global list (one atomic per wave).
 //   k_scan_tasks  one lane per task: the scans that go on, to their end or the LZ_LUT_MAXWIN cap; full waves.
-//   k_partition   keys + summaries -> records, stably partitioned into the 256 streams (tile histogram of k_hist).
+//   k_partition   keys + summaries -> records, every tile stably sorted by partition in place (+ the tile tables).
 // (One fused kernel did all of this per tile behind barriers: its workgroups spent half their time in the light
 // phases -- queue drain on two waves, ranks, write-out -- while holding the LDS and the wave slots the scans need.)
 struct LzScanTask { u32 idx; s32 diag; LzLutScan L, R; };
@@ -995,7 +976,7 @@ k_scan_hits(LzExtendParams P, LzLutParams Q, const u64* __restrict__ keys, u64 n
         }
     } else if (span < nspans) {
         // A wave takes 256 consecutive hits (a span); a LANE takes four consecutive ones, one per round: its keys are two 16-byte loads,
-        // its four summaries one 16-byte store, its four partition bytes (for k_hist) one 4-byte store -- 64 consecutive bytes of a
+        // its four summaries one 16-byte store, its four partition bytes one 4-byte store -- 64 consecutive bytes of a
         // span's 256 went out per round when a lane's hits were 64 apart (the partition bytes as 64 one-byte stores: +2 ms on the 50 Mbp
         // pair; the fill kernel used to write them beside its keys, in runs of ~39 bytes at random places, two partial lines each: 4-7 of
         // its 19-26 ms).  The windows of a round are requested one round ahead into two register sets that take turns (no copies), the
@@ -1081,31 +1062,67 @@ k_scan_tasks(LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut
     }
 }
 
-// keys + summaries -> records in their partitions.  One workgroup per tile of k_hist; a wave owns 256 consecutive
-// hits (64 per round), so ranks by (wave, round, lane) follow the discovery order.
+// keys + summaries -> records, every tile sorted by partition where it lies (lz_tile_runs.hpp).  One workgroup per tile;
+// a wave owns 256 consecutive hits (64 per round), so ranks by (wave, round, lane) follow the discovery order.
 struct LzPartShared {
-    union {
-        u64 stage[LZ_PP_TILE];                       // the tile's records, ordered by partition (the partition rides in bits 55..62)
-        u64 bm[LZ_PP_WAVES][LZ_NBIN];                // BM: peer bitmaps of the round in flight (all zero again before stage[] is written)
+    union alignas(16) {
+        u64 stage[LZ_PP_TILE];                       // the tile's records, ordered by partition
+        u64 bm[LZ_PP_WAVES][LZ_NBIN];                // peer bitmaps of the round in flight (all zero again before stage[] is written)
     };
     u32 wcnt[LZ_PP_WAVES][LZ_NBIN];                  // per wave and partition: records / running offset inside the partition
-    u32 tstart[LZ_NBIN + 1], gbase[LZ_NBIN], wtot[4];
+    u32 tstart[LZ_NBIN], wtot[4];
 };
-// BM == false: round 2's ranks (LDS atomics count, an 8-ballot match ranks: half of the kernel's 161 VALU instructions
-// per hit).  BM == true: the lanes of a round that hold the same partition find each other through a 64-bit bitmap
-// in LDS (atomic OR of 1 << lane, one read; the result does not depend on the order of the ORs), which gives rank
-// and count in one pass and leaves the per-wave totals behind -- no separate counting pass, no ballots.
-template <bool BM>
+static_assert(LZ_PP_TILE == LZ_PP_TILE_HOST, "lz_tile_runs.hpp addresses runs by the tile size");
+// The lanes of a round that hold the same partition find each other through a 64-bit bitmap in LDS (atomic OR of
+// 1 << lane, one read; the result does not depend on the order of the ORs), which gives rank and count in one pass and
+// leaves the per-wave totals behind -- no separate counting pass, no ballots.  bin = the partition of record k of the lane.
+// Ends behind a barrier with the per-partition counts chained in wave order in wcnt, the tile-local starts in tstart,
+// and the tile's two table rows written.
+#define LZ_PART_RANKS(BIN_OF_)                                                                                         \
+    u32 slot[LZ_PP_ROUNDS];                                                                                            \
+    _Pragma("unroll")                                                                                                  \
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {                                                                           \
+        /* (each wave works on its own rows of bm / wcnt: LDS operations of one wave execute in order) */              \
+        const bool valid = l0 + 64u * r < tile_n;                                                                      \
+        const u32 bin = BIN_OF_(r);                                                                                    \
+        if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);                                        \
+        const u64 peers = valid ? sh.bm[w][bin] : 0ull;                                                                \
+        const u32 old = valid ? sh.wcnt[w][bin] : 0u;                                                                  \
+        if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }  /* the highest peer */ \
+        slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));                                                \
+    }                                                                                                                  \
+    __syncthreads();                                                                                                   \
+    u32 tot = 0;                                                                                                       \
+    if (tid < LZ_NBIN) for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }   \
+    const u32 ts = lz_exscan256(tot, sh.wtot);                                                                         \
+    if (tid < LZ_NBIN) {                                                                                               \
+        sh.tstart[tid] = ts;                                                                                           \
+        hist[(size_t)tile * LZ_NBIN + tid] = tot;                                                                      \
+        run_addr[(size_t)tile * LZ_NBIN + tid] = lz_tr_run_addr(tile, ts);                                             \
+    }                                                                                                                  \
+    __syncthreads();
+// the staged tile -> its own place in the record array, tags cleared: 16 bytes per lane, whole lines per wave
+__device__ __forceinline__ void lz_part_store(const u64* stage, u32 tile_n, u64* out /*the tile's first record*/)
+{
+    typedef u64 lz_u64x2 __attribute__((ext_vector_type(2)));
+    for (u32 k = threadIdx.x * 2u; k < tile_n; k += LZ_PP_TPB * 2u) {
+        lz_u64x2 v = *reinterpret_cast<const lz_u64x2*>(stage + k);     // (k + 1 == tile_n: stage[k + 1] is inside stage[] and not stored)
+        v.x = LZ_REC_UNTAG(v.x); v.y = LZ_REC_UNTAG(v.y);
+        if (k + 1u < tile_n) *reinterpret_cast<lz_u64x2*>(out + k) = v;
+        else out[k] = v.x;
+    }
+}
+// recs may be keys (the sort is in place then): every record of the tile is in registers before the first store, and no
+// other workgroup touches the tile
 __global__ void __launch_bounds__(LZ_PP_TPB)
-k_partition(const u64* __restrict__ keys, const u32* __restrict__ summ, u64 n,
-            const u32* __restrict__ hist, const u32* __restrict__ part, u64* __restrict__ recs)
+k_partition(const u64* keys, const u32* __restrict__ summ, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr, u64* recs)
 {
     __shared__ LzPartShared sh;
     const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const u32 tile = blockIdx.x;
     const u64 base = (u64)tile * LZ_PP_TILE;
     const u32 tile_n = (n - base < (u64)LZ_PP_TILE) ? (u32)(n - base) : (u32)LZ_PP_TILE;
-    for (u32 k = tid; k < LZ_PP_WAVES * LZ_NBIN; k += LZ_PP_TPB) { (&sh.wcnt[0][0])[k] = 0; if (BM) (&sh.bm[0][0])[k] = 0ull; }
+    for (u32 k = tid; k < LZ_PP_WAVES * LZ_NBIN; k += LZ_PP_TPB) { (&sh.wcnt[0][0])[k] = 0; (&sh.bm[0][0])[k] = 0ull; }
     const u32 l0 = w * (64u * LZ_PP_ROUNDS) + lane;
     u64 kk[LZ_PP_ROUNDS]; u32 ss[LZ_PP_ROUNDS];
 #pragma unroll
@@ -1115,56 +1132,18 @@ k_partition(const u64* __restrict__ keys, const u32* __restrict__ summ, u64 n,
         ss[r] = v ? summ[base + l0 + 64u * r] : 0u;
     }
     __syncthreads();
-    u32 slot[BM ? LZ_PP_ROUNDS : 1];
-    if (BM) {
-        // (each wave works on its own rows of bm / wcnt: LDS operations of one wave execute in order)
-#pragma unroll
-        for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
-            const bool valid = l0 + 64u * r < tile_n;
-            const u32 bin = LZ_KEY_BIN(kk[r]);
-            if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);
-            const u64 peers = valid ? sh.bm[w][bin] : 0ull;
-            const u32 old = valid ? sh.wcnt[w][bin] : 0u;
-            if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }   // the highest peer
-            slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));
-        }
-    } else {
-#pragma unroll
-        for (u32 r = 0; r < LZ_PP_ROUNDS; r++) if (l0 + 64u * r < tile_n) atomicAdd(&sh.wcnt[w][LZ_KEY_BIN(kk[r])], 1u);
-    }
-    __syncthreads();
-    // per-partition counts chained in wave order (= discovery order) ...
-    u32 tot = 0;
-    if (tid < LZ_NBIN) {
-        for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }
-        sh.gbase[tid] = part[(size_t)(tile >> 8) * LZ_NBIN + tid] + hist[(size_t)tile * LZ_NBIN + tid];
-    }
-    const u32 ts = lz_exscan256(tot, sh.wtot);
-    if (tid < LZ_NBIN) sh.tstart[tid] = ts;
-    if (tid == 0) sh.tstart[LZ_NBIN] = tile_n;
-    __syncthreads();
-    // ... then every record gets its place: rank among the same-partition lanes of its wave's round, on top of
-    // the wave's running offset (stable: lanes, rounds and waves all follow the discovery order)
+#define LZ_PART_BIN(r_) LZ_KEY_BIN(kk[r_])
+    LZ_PART_RANKS(LZ_PART_BIN)
+#undef LZ_PART_BIN
+    // every record gets its place: rank among the same-partition lanes of its wave's round, on top of the wave's
+    // running offset (stable: lanes, rounds and waves all follow the discovery order)
 #pragma unroll
     for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
-        const bool valid = l0 + 64u * r < tile_n;
         const u32 bin = LZ_KEY_BIN(kk[r]);
-        if (BM) {
-            if (valid) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = lz_hit_record(kk[r], ss[r]) | ((u64)bin << 55);
-        } else {
-            u32 rank, count; bool last;
-            lz_match8(bin, valid, lane, rank, count, last);
-            const u32 old = sh.wcnt[w][bin];
-            if (valid && last) sh.wcnt[w][bin] = old + count;
-            if (valid) sh.stage[sh.tstart[bin] + old + rank] = lz_hit_record(kk[r], ss[r]) | ((u64)bin << 55);
-        }
+        if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = lz_hit_record(kk[r], ss[r]);
     }
     __syncthreads();
-    for (u32 k = tid; k < tile_n; k += LZ_PP_TPB) {
-        const u64 r = sh.stage[k];
-        const u32 b = (u32)(r >> 55) & 0xFFu;
-        recs[(size_t)sh.gbase[b] + (k - sh.tstart[b])] = r & ~(0xFFull << 55);
-    }
+    lz_part_store(sh.stage, tile_n, recs + base);
 }
 
 // grid of k_scan_hits for n hits, and the geometry of its task list: one region per wave, room for 1/32 of the
@@ -1237,14 +1216,12 @@ int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const Lz
     return 0;
 }
 
-int lzk_partition(LzCtx& c, int set, const u64* keys, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st)
+int lzk_partition(LzCtx& c, int set, u64* keys, u64 n, u32* hist, u32* run_addr, hipStream_t st)
 {
     if (n == 0) return 0;
     const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
     c.timer.begin("k_partition", st);
-    static const bool ballots = getenv("LZGPU_PARTITION_BALLOTS") != nullptr;  // A/B aid: round 2's ballot-match ranks
-    if (ballots) hipLaunchKernelGGL(k_partition<false>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, part, recs);
-    else         hipLaunchKernelGGL(k_partition<true>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, part, recs);
+    hipLaunchKernelGGL(k_partition, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, run_addr, keys);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;
@@ -1260,7 +1237,7 @@ int lzk_partition(LzCtx& c, int set, const u64* keys, u64 n, const u32* hist, co
 //                  discovery order.  No keys, no summaries, no partition bytes.  Persistent waves (the 64 KiB tables are
 //                  loaded once per workgroup) that stride over the 64-entry groups of the sorted list.
 //   k_scan_tasks2  replaces the provisional record a queued hit left (payload and SLOW flag were missing).
-//   k_hist2 / k_partition2   read the tagged records (the partition rides in bits 55..62).
+//   k_partition2   sorts the tagged records in place (the partition rides in bits 55..62).
 __global__ void __launch_bounds__(LZ_TPB)
 k_build_wctx(const u32* __restrict__ wpos, u64 num_words, const u8* __restrict__ two, LzVec16* __restrict__ wctx)
 {
@@ -1440,29 +1417,9 @@ k_scan_tasks2(LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lu
     }
 }
 
-__global__ void __launch_bounds__(LZ_TPB)
-k_hist2(const u64* __restrict__ tagged, u64 n, u32* __restrict__ hist)
-{
-    __shared__ u32 cnt[LZ_NBIN];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const u64 base = (u64)blockIdx.x * LZ_PP_TILE;
-    typedef u64 lz_u64x2 __attribute__((ext_vector_type(2)));
-#pragma unroll 4
-    for (int r = 0; r < LZ_PP_TILE / (LZ_TPB * 2); r++) {       // two records per lane and step
-        const u64 i = base + ((u64)r * LZ_TPB + threadIdx.x) * 2u;
-        if (i + 1u < n) {
-            const lz_u64x2 v = *reinterpret_cast<const lz_u64x2*>(tagged + i);
-            atomicAdd(&cnt[LZ_REC_TAG(v.x)], 1u); atomicAdd(&cnt[LZ_REC_TAG(v.y)], 1u);
-        } else if (i < n) atomicAdd(&cnt[LZ_REC_TAG(tagged[i])], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)blockIdx.x * LZ_NBIN + threadIdx.x] = cnt[threadIdx.x];
-}
-
-// k_partition<true> on tagged records
+// k_partition on tagged records, in place
 __global__ void __launch_bounds__(LZ_PP_TPB)
-k_partition2(const u64* __restrict__ tagged, u64 n, const u32* __restrict__ hist, const u32* __restrict__ part, u64* __restrict__ recs)
+k_partition2(u64* recs, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr)
 {
     __shared__ LzPartShared sh;
     const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
@@ -1473,40 +1430,18 @@ k_partition2(const u64* __restrict__ tagged, u64 n, const u32* __restrict__ hist
     const u32 l0 = w * (64u * LZ_PP_ROUNDS) + lane;
     u64 rr[LZ_PP_ROUNDS];
 #pragma unroll
-    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) rr[r] = (l0 + 64u * r < tile_n) ? tagged[base + l0 + 64u * r] : 0ull;
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) rr[r] = (l0 + 64u * r < tile_n) ? recs[base + l0 + 64u * r] : 0ull;
     __syncthreads();
-    u32 slot[LZ_PP_ROUNDS];
-#pragma unroll
-    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
-        const bool valid = l0 + 64u * r < tile_n;
-        const u32 bin = LZ_REC_TAG(rr[r]);
-        if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);
-        const u64 peers = valid ? sh.bm[w][bin] : 0ull;
-        const u32 old = valid ? sh.wcnt[w][bin] : 0u;
-        if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }
-        slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));
-    }
-    __syncthreads();
-    u32 tot = 0;
-    if (tid < LZ_NBIN) {
-        for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }
-        sh.gbase[tid] = part[(size_t)(tile >> 8) * LZ_NBIN + tid] + hist[(size_t)tile * LZ_NBIN + tid];
-    }
-    const u32 ts = lz_exscan256(tot, sh.wtot);
-    if (tid < LZ_NBIN) sh.tstart[tid] = ts;
-    if (tid == 0) sh.tstart[LZ_NBIN] = tile_n;
-    __syncthreads();
+#define LZ_PART_BIN(r_) LZ_REC_TAG(rr[r_])
+    LZ_PART_RANKS(LZ_PART_BIN)
+#undef LZ_PART_BIN
 #pragma unroll
     for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
         const u32 bin = LZ_REC_TAG(rr[r]);
         if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = rr[r];
     }
     __syncthreads();
-    for (u32 k = tid; k < tile_n; k += LZ_PP_TPB) {
-        const u64 r = sh.stage[k];
-        const u32 b = LZ_REC_TAG(r);
-        recs[(size_t)sh.gbase[b] + (k - sh.tstart[b])] = LZ_REC_UNTAG(r);
-    }
+    lz_part_store(sh.stage, tile_n, recs + base);
 }
 
 int lzk_wctx_build(LzCtx& c)
@@ -1581,25 +1516,12 @@ int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, con
     LZ_HIP(hipGetLastError());
     return 0;
 }
-int lzk_hist_tagged(LzCtx& c, const u64* tagged, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st)
-{
-    const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE), nblocks = (ntiles + 255u) / 256u;
-    c.timer.begin("k_hist", st);
-    hipLaunchKernelGGL(k_hist2, dim3(ntiles), dim3(LZ_TPB), 0, st, tagged, n, hist);
-    c.timer.end(st);
-    c.timer.begin("k_hist_scan", st);
-    hipLaunchKernelGGL(k_hist_scan1, dim3(nblocks), dim3(LZ_NBIN), 0, st, hist, ntiles, part);
-    hipLaunchKernelGGL(k_hist_scan2, dim3(1), dim3(LZ_NBIN), 0, st, part, nblocks, bin_base);
-    c.timer.end(st);
-    LZ_HIP(hipGetLastError());
-    return 0;
-}
-int lzk_partition_tagged(LzCtx& c, const u64* tagged, u64 n, const u32* hist, const u32* part, u64* recs, hipStream_t st)
+int lzk_partition_tagged(LzCtx& c, u64* tagged, u64 n, u32* hist, u32* run_addr, hipStream_t st)
 {
     if (n == 0) return 0;
     const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
     c.timer.begin("k_partition", st);
-    hipLaunchKernelGGL(k_partition2, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, tagged, n, hist, part, recs);
+    hipLaunchKernelGGL(k_partition2, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, tagged, n, hist, run_addr);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;
@@ -1728,9 +1650,13 @@ struct LzSettle2Shared {
     u32 cnt[2][LZ_S2_SORTW][LZ_NBIN];                    // records per (wave, bucket) of the tile being counted / placed
     u32 woff[LZ_S2_SORTW][LZ_NBIN];                      // where wave w's records of bucket b start in the placed tile
     u32 lbeg[2][LZ_NBIN], lcnt[2][LZ_NBIN];              // bucket lists of the placed tiles
+    alignas(8) u8 own[LZ_S2_SORTW][64 * LZ_S2_ROUNDS];   // load_tile: per rank of a wave's window, 1 + the block entry of the run that starts there
 };
+static_assert(sizeof(LzSettle2Shared) <= 160 * 1024, "k_settle2: one workgroup per CU");
+static_assert(LZ_TR_BLOCK <= 255 && (64 * LZ_S2_ROUNDS) % 8 == 0, "own[] holds 1 + a block entry per byte, cleared 8 at a time");
 __global__ void __launch_bounds__(LZ_S2_TPB)
-k_settle2(LzExtendParams P, const u64* __restrict__ recs, const u32* __restrict__ bin_base, u32* __restrict__ diag_end,
+k_settle2(LzExtendParams P, const u64* __restrict__ recs, u32 n_pp_tiles, const u32* __restrict__ hist, const u32* __restrict__ hist_part,
+          const u32* __restrict__ run_addr, const u32* __restrict__ bin_base, u32* __restrict__ diag_end,
           const s32* __restrict__ score_tab_g, LzHspRec* __restrict__ out, u32* __restrict__ out_count, u32 out_cap,
           u64* __restrict__ counters)
 {
@@ -1750,12 +1676,71 @@ k_settle2(LzExtendParams P, const u64* __restrict__ recs, const u32* __restrict_
     // ---- sorter pieces
     u64 cx[LZ_S2_ROUNDS], nx[LZ_S2_ROUNDS];                     // records of the tile to place next / to count next
     u32 cslot[LZ_S2_ROUNDS];
-    auto load_tile = [&](u32 tt, u64* x) {                      // (sorters) the wave's 256 records of tile tt, 64 per round
+    // The partition's records lie in one run per partition tile (lz_tile_runs.hpp).  A sorter wave keeps a block of
+    // LZ_TR_BLOCK consecutive tiles' (first rank, address) of the partition, LZ_TR_K per lane (lane l: tiles cur + K l ..),
+    // that only moves forward; window_first(tt) = the first rank of the wave's window of tile tt.
+    u32 cur = 0, bf[LZ_TR_K], ba[LZ_TR_K];
+    auto load_block = [&]() {
 #pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
-            const u64 li = (u64)tt * LZ_S2_TILE + sw * (64u * LZ_S2_ROUNDS) + (u32)rr * 64u + lane;
-            x[rr] = (tt < ntiles && li < (u64)n) ? LZ_NT_LD(recs + (size_t)r0 + li) : ~0ull;       // ~0: no record
+        for (int j = 0; j < LZ_TR_K; j++) {
+            const u32 t = cur + lane * LZ_TR_K + (u32)j;
+            bf[j] = lz_tr_first(hist, hist_part, n_pp_tiles, t, part, r1);
+            ba[j] = t < n_pp_tiles ? run_addr[(size_t)t * LZ_NBIN + part] : 0u;
         }
+    };
+    auto block_end = [&]() -> u32 { return (u32)__builtin_amdgcn_readlane((int)bf[LZ_TR_K - 1], 63); };
+    auto window_first = [&](u32 tt) -> u32 { return r0 + tt * (u32)LZ_S2_TILE + sw * (64u * LZ_S2_ROUNDS); };
+    // one step of the cursor ahead of load_tile(tt), where the loads have a whole placement to arrive (the usual tile
+    // needs no more than this one: 5376 ranks are about 84 partition tiles)
+    auto advance_early = [&](u32 tt) {
+        if (tt < ntiles && window_first(tt) < r1 && lz_tr_block_behind(block_end(), window_first(tt))) { cur += LZ_TR_BLOCK - 1; load_block(); }
+    };
+    auto load_tile = [&](u32 tt, u64* x) {                      // (sorters) the wave's 448 records of tile tt, 64 per round
+#pragma unroll
+        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) x[rr] = ~0ull;                                    // ~0: no record
+        const u32 g0 = window_first(tt);
+        if (tt >= ntiles || g0 >= r1) return;                   // (wave-uniform)
+        const u32 g1 = (r1 - g0 < 64u * LZ_S2_ROUNDS) ? r1 : g0 + 64u * LZ_S2_ROUNDS;
+        u8* const own = sh.own[sw];
+        u32 idx[LZ_S2_ROUNDS] = {};
+        for (;;) {
+            const u32 bend = block_end();
+            if (!lz_tr_block_behind(bend, g0)) {
+                // the runs of the block that hold ranks of the window mark their first one with 1 + their entry; a
+                // running maximum over the window then names every rank's run (k_fill_hits2's own[])
+                if (lane < 64u * LZ_S2_ROUNDS / 8u) reinterpret_cast<u64*>(own)[lane] = 0ull;
+                u32 dl[LZ_TR_K];
+#pragma unroll
+                for (int j = 0; j < LZ_TR_K; j++) {
+                    const u32 nf = j + 1 < LZ_TR_K ? bf[(j + 1) % LZ_TR_K] : (u32)__shfl_down((int)bf[0], 1);    // the next tile's first rank
+                    u32 pos;
+                    const bool m = lz_tr_mark(bf[j], nf, g0, g1, pos) && !(j == LZ_TR_K - 1 && lane == 63u);   // (the last entry only bounds the block)
+                    if (m) own[pos] = (u8)(1u + lane * LZ_TR_K + (u32)j);
+                    dl[j] = lz_tr_delta(ba[j], bf[j]);
+                }
+                const u32 bfirst = (u32)__builtin_amdgcn_readlane((int)bf[0], 0);
+                u32 carry = 0;
+#pragma unroll
+                for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
+                    const u32 g = g0 + (u32)rr * 64u + lane;
+                    const u32 mk = own[(u32)rr * 64u + lane];
+                    u32 v = mk;
+                    LZ_WAVE_SCAN_U32(v, mk, lz_umax)
+                    v = lz_umax(v, carry);
+                    carry = (u32)__builtin_amdgcn_readlane((int)v, 63);
+                    const u32 e = v - 1u;                       // (v == 0: a rank below the block, not covered)
+                    u32 d = (u32)__shfl((int)dl[0], (int)(e / LZ_TR_K));
+#pragma unroll
+                    for (int j = 1; j < LZ_TR_K; j++) { const u32 dj = (u32)__shfl((int)dl[j], (int)(e / LZ_TR_K)); if (e % LZ_TR_K == (u32)j) d = dj; }
+                    if (lz_tr_covers(g, bfirst, bend, g1)) idx[rr] = lz_tr_index(g, d);
+                }
+                if (bend >= g1) break;
+            }
+            cur += LZ_TR_BLOCK - 1; load_block();               // (a sparse partition: the window goes on in later tiles)
+        }
+#pragma unroll
+        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
+            if (g0 + (u32)rr * 64u + lane < g1) x[rr] = LZ_NT_LD(recs + (size_t)idx[rr]);
     };
     auto count_tile = [&](u32 tt, const u64* x, u32* slot) {    // ranks inside (wave, bucket) -> slot[], totals -> cnt[tt & 1][sw][]
         u32* const row = sh.cnt[tt & 1u][sw];
@@ -1804,6 +1789,7 @@ k_settle2(LzExtendParams P, const u64* __restrict__ recs, const u32* __restrict_
     __syncthreads();                                            // tab, bm
     if (!walker) {
         // prologue: tile 0 counted | tile 0 placed, tile 1 counted | then per interval t: tile t+1 placed, tile t+2 counted
+        load_block();
         load_tile(0, cx); load_tile(1, nx); count_tile(0, cx, cslot);
         __syncthreads();
         place_tile(0, cx, cslot);
@@ -1814,6 +1800,7 @@ k_settle2(LzExtendParams P, const u64* __restrict__ recs, const u32* __restrict_
         __syncthreads();
         for (u32 t = 0; t < ntiles; t++) {
             LZ_S2_CLK_BEGIN(sw == 0 && lane == 0);
+            advance_early(t + 3);
             if (t + 1 < ntiles) place_tile(t + 1, cx, cslot);
 #pragma unroll
             for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) cx[rr] = nx[rr];
@@ -1915,13 +1902,15 @@ k_settle2(LzExtendParams P, const u64* __restrict__ recs, const u32* __restrict_
     }
 }
 
-int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, const u32* bin_base, u32* diag_end,
-               const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s)
+int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, u64 n, const u32* hist, const u32* hist_part, const u32* run_addr,
+               const u32* bin_base, u32* diag_end, const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s)
 {
+    if (n == 0) return 0;
+    const u32 n_pp_tiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
     c.timer.begin("k_settle2", s);
     static bool attr_set = false;
     if (!attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_settle2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzSettle2Shared))); attr_set = true; }
-    hipLaunchKernelGGL(k_settle2, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), s, P, recs, bin_base, diag_end, score_tab, out, out_count, out_cap, counters);
+    hipLaunchKernelGGL(k_settle2, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), s, P, recs, n_pp_tiles, hist, hist_part, run_addr, bin_base, diag_end, score_tab, out, out_count, out_cap, counters);
     c.timer.end(s);
     LZ_HIP(hipGetLastError());
     return 0;
