@@ -179,8 +179,8 @@ int lzgpu_seed_hit_search(const lz_search_args* args, lz_hsp** out, uint64_t* n_
  * its length must equal the target's.  same_strand = (seq1->revCompFlags == seq2->revCompFlags) (:373).  The
  * separators of a [multi] sequence are its partitions' sepBefore values plus the final NUL, as lz_gapped_args takes
  * them; both counts 0 for a sequence without partitions.  A band with opposite strands, separator counts that differ
- * (or equal 1, or are not ascending inside the sequence), a query of another length, bucket owners
- * (lzgpu_set_bucket_owner) or LZGPU_FILL_SHUFFLE return LZGPU_NH_UNSUPPORTED before any work is done. */
+ * (or equal 1, or are not ascending inside the sequence), a query of another length or bucket owners
+ * (lzgpu_set_bucket_owner) return LZGPU_NH_UNSUPPORTED before any work is done. */
 typedef struct lz_self_args {
     int32_t         same_strand;   /* selfCompare && seq1->revCompFlags == seq2->revCompFlags        */
     uint32_t        band_width;    /* --band (0: none); only with same_strand                        */

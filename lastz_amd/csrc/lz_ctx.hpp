@@ -144,12 +144,11 @@ int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStrea
 int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n);
 int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
                   const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ[set], and the partition byte of every hit -> bins
-int lzk_partition(LzCtx& c, int set, u64* keys, u64 n, u32* hist, u32* run_addr, hipStream_t st);        // keys -> records, in place
+int lzk_partition(LzCtx& c, bool tagged, u64* recs, const u32* summ, u64 n, u32* hist, u32* run_addr, hipStream_t st);   // keys + summaries (or tagged records: summ unused) -> records, in place
 // the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records instead of keys / summaries / partition bytes
 int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
 int lzk_fused_reserve(LzCtx& c, int set, u64 max_n);
 int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
                    const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st);
-int lzk_partition_tagged(LzCtx& c, u64* tagged, u64 n, u32* hist, u32* run_addr, hipStream_t st);         // tagged records -> records, in place
 int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, u64 n, const u32* hist, const u32* hist_part, const u32* run_addr,
                const u32* bin_base, u32* diag_end, const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);

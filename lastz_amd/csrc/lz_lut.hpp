@@ -304,7 +304,7 @@ LZ_HD u64 lz_hit_record(u64 key, u32 summ)
     return (u64)pos2 | ((u64)(diag & 0xFFu) << 31) | (payload << 39) | (slow ? (1ull << 63) : 0ull);
 }
 // the record with its partition (bits 8..15 of hashedDiag) riding in the free bits 55..62: the form k_scan_hits2 stores
-// and k_partition2 reads; it clears the tag when it writes the record to its place in the sorted tile
+// and k_partition<true> reads; it clears the tag when it writes the record to its place in the sorted tile
 #define LZ_REC_TAG(r)     ((u32)((r) >> 55) & 0xFFu)
 #define LZ_REC_UNTAG(r)   ((r) & ~(0xFFull << 55))
 LZ_HD u64 lz_hit_record_tagged(u64 key, u32 summ) { return lz_hit_record(key, summ) | ((u64)((u32)(key >> 40) & 0xFFu) << 55); }

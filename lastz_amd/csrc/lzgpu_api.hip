@@ -672,10 +672,10 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     const int nsets = overlap ? (int)std::min<size_t>(chunks.size() ? chunks.size() : 1, LZ_SETS) : 1;
     // scan mode 0 takes the fused path (k_scan_hits2: enumeration + phase A over the context-inlined table, tagged
     // records in keys[] and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
-    // the fill variant in use is one the fused kernel does not reproduce (bucket owners, LZGPU_FILL_SHUFFLE), or
+    // the fill variant in use is one the fused kernel does not reproduce (bucket owners), or
     // wctx cannot be had (lz_wctx_prepare)
     static const bool fused_off = getenv("LZGPU_FUSED_SCAN") != nullptr && atoi(getenv("LZGPU_FUSED_SCAN")) == 0;
-    bool fused = a->extend && mode == 0 && max_chunk && !fused_off && c.n_owners <= 1 && getenv("LZGPU_FILL_SHUFFLE") == nullptr;
+    bool fused = a->extend && mode == 0 && max_chunk && !fused_off && c.n_owners <= 1;
     if (fused && (rc = lz_wctx_prepare(c, fused))) return rc;
     if (max_chunk) {
         if ((rc = c.keys[0].ensure((size_t)max_chunk * 8))) return rc;
@@ -751,7 +751,7 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
                                      c.lut.as<LzLutEntry>(), c.keys[set].as<u64>(), sS))) return rc;
             LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
             LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-            if ((rc = lzk_partition_tagged(c, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
+            if ((rc = lzk_partition(c, true, c.keys[set].as<u64>(), nullptr, ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
             if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
             set_n[set] = ch.nh;
             LZ_HIP(hipEventRecord(c.ev_part[set], sB));
@@ -768,7 +768,7 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
         LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
         // B: the partition
         LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-        if ((rc = lzk_partition(c, set, c.keys[set].as<u64>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
+        if ((rc = lzk_partition(c, false, c.keys[set].as<u64>(), c.summ[set].as<u32>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
         if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
         set_n[set] = ch.nh;
         LZ_HIP(hipEventRecord(c.ev_part[set], sB));
@@ -860,8 +860,8 @@ extern "C" int lzgpu_seed_hit_search_self(const lz_search_args* a, const lz_self
         if (s->sep1[k] > qlen || s->sep2[k] > qlen) return LZGPU_NH_UNSUPPORTED;
         if (k && (s->sep1[k] <= s->sep1[k - 1] || s->sep2[k] <= s->sep2[k - 1])) return LZGPU_NH_UNSUPPORTED;
     }
-    // only k_count_sorted_self and k_fill_hits2<true> clip: not with bucket owners or the shuffle fill
-    if (c.n_owners > 1 || getenv("LZGPU_FILL_SHUFFLE") != nullptr) return LZGPU_NH_UNSUPPORTED;
+    // only k_count_sorted_self, k_fill_hits2<true> and k_scan_hits2<true> clip: not with bucket owners
+    if (c.n_owners > 1) return LZGPU_NH_UNSUPPORTED;
 
     LzSelfDev sd = {};
     sd.L = (u32)c.seed.length; sd.len2 = qlen; sd.band = s->same_strand ? s->band_width : 0u;

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <cstdio>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -397,14 +398,15 @@ int lzk_sample_offsets(LzCtx& c, const u64* off, const u32* cnt, u32 n, u32 stri
 }
 
 // B2 step 2: materialise the hits of query positions [i0,i1) in discovery order.
+// k_fill_hits is the fill of a process that owns a share of the buckets (lzgpu_set_bucket_owner); every other search
+// goes through k_fill_hits2 or k_scan_hits2 below.
 // A wave takes 64 entries of the word-sorted list, keeps those whose position lies in [i0,i1) (the hit
 // arrays hold one chunk of positions at a time) and serves them four at a time: 16 lanes per position, one
-// probe (exact word / transition flip) per lane.  Each lane reads its word's CSR range, a 16-lane prefix
-// sum places the probes' lists back to back in probe order (= the reference's enumeration order within a
-// position, src/seed_search.c:522-549), and the lists go to off[position] in the hit array.
+// probe (exact word / transition flip) per lane.  Each lane reads its word's CSR range and counts the hits it owns, a
+// 16-lane prefix sum places the probes' lists back to back in probe order (= the reference's enumeration order within a
+// position, src/seed_search.c:522-549), and every lane writes its list's owned hits from off[position] on.
 #define LZ_KEY_BIN(k)  ((u32)((k) >> 40) & 0xFFu)    // the partition of a hit: bits 8..15 of hashedDiag
 #define LZ_FILL_GROUP 16
-template <bool OWNED>
 __global__ void __launch_bounds__(LZ_TPB)
 k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
             const u32* __restrict__ wstart, const u32* __restrict__ wpos,
@@ -437,8 +439,8 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
             u32 a = 0, len = 0, full = 0;
             if (have && r + (int)p < sd.nprobes) {
                 const u32 w = packed ^ sd.probe_xor[r + p];
-                a = wstart[w]; full = wstart[w + 1] - a; len = full;
-                if (OWNED) { len = 0; for (u32 jj = 0; jj < full; jj++) len += lz_owned(wpos[a + jj], pos2, n_owners, owner) ? 1u : 0u; }
+                a = wstart[w]; full = wstart[w + 1] - a;
+                for (u32 jj = 0; jj < full; jj++) len += lz_owned(wpos[a + jj], pos2, n_owners, owner) ? 1u : 0u;
             }
             u32 incl = len;                                  // inclusive prefix over the 16-lane group
 #pragma unroll
@@ -447,38 +449,8 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
                 if ((int)p >= d) incl += v;
             }
             const u32 total = __shfl(incl, LZ_FILL_GROUP - 1, LZ_FILL_GROUP);
-            if (OWNED) {
-                u64* o = out + carry + (incl - len);
-                for (u32 jj = 0; jj < full; jj++) { const u32 p1 = wpos[a + jj]; if (lz_owned(p1, pos2, n_owners, owner)) *o++ = lz_hit_key(p1, pos2); }
-            } else {
-                // The (up to) 64 lists of the wave -- 4 positions x 16 probes -- laid end to end: lane t takes hit t,
-                // t + 64, ... of that run, finds the list holding it (binary search over the lanes' running totals)
-                // and writes it to its place: the stores of a wave are consecutive keys (one run per position),
-                // not one 8-byte store per list and step.
-                u32 gtot = total;                             // running totals over the whole wave: + the groups below
-                const u32 t0 = __shfl(total, 0), t1 = __shfl(total, 16), t2 = __shfl(total, 32), t3 = __shfl(total, 48);
-                const u32 gbase = g == 0 ? 0u : g == 1 ? t0 : g == 2 ? t0 + t1 : t0 + t1 + t2;      // hits of the groups below this lane's
-                gtot = t0 + t1 + t2 + t3;
-                const u32 winc = gbase + incl;                // inclusive running total at this lane
-                const s64 obase = have ? (s64)(out - keys) + (s64)carry - (s64)gbase : 0;           // key index of the group's run, minus gbase
-                for (u32 tb = 0; tb < gtot; tb += 64u) {      // wave-uniform trips: every lane takes part in the shuffles
-                    const u32 t = tb + lane;
-                    u32 lo_l = 0, hi_l = 63;                  // first lane whose inclusive total exceeds t
-#pragma unroll
-                    for (int it = 0; it < 6; it++) {
-                        const u32 mid = (lo_l + hi_l) >> 1;
-                        const u32 v = (u32)__shfl((int)winc, (int)mid);
-                        if (v > t) hi_l = mid; else lo_l = mid + 1;
-                    }
-                    const u32 L = lo_l;
-                    const u32 l_inc = (u32)__shfl((int)winc, (int)L), l_len = (u32)__shfl((int)len, (int)L), l_a = (u32)__shfl((int)a, (int)L);
-                    const u32 l_pos2 = (u32)__shfl((int)pos2, (int)L);
-                    const u32 ob_lo = (u32)__shfl((int)(u32)obase, (int)L), ob_hi = (u32)__shfl((int)(u32)((u64)obase >> 32), (int)L);
-                    const u32 jj = t - (l_inc - l_len);
-                    const s64 ob = (s64)(((u64)ob_hi << 32) | ob_lo);
-                    if (t < gtot) keys[ob + (s64)t] = lz_hit_key(wpos[l_a + jj], l_pos2);
-                }
-            }
+            u64* o = out + carry + (incl - len);
+            for (u32 jj = 0; jj < full; jj++) { const u32 p1 = wpos[a + jj]; if (lz_owned(p1, pos2, n_owners, owner)) *o++ = lz_hit_key(p1, pos2); }
             carry += total;
         }
     }
@@ -486,7 +458,7 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 
 
 // ---- k_fill_hits2 (round 4): the same hits at the same places, the lists found through LDS instead of shuffles.
-// k_fill_hits lays the 64 lists of four positions end to end and lets every lane search the running totals for the list
+// Round 2's fill (DESIGN_HISTORY.md) laid the 64 lists of four positions end to end and let every lane search the running totals for the list
 // holding its hit: 13 shuffles and two prefix sums per 64 hits, 150 VALU instructions per 64-hit trip for 16 bytes of
 // useful traffic per hit.  Here a wave takes its 64 sorted entries at once:
 //   1. every lane reads the CSR bounds of its position's probes (13 independent pairs of loads in flight per lane)
@@ -500,13 +472,15 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 //      stores of a wave are runs of consecutive keys (one run per position), as before.
 // A wave's LDS traffic is its own (no barrier: LDS operations of one wave execute in program order); concatenations
 // longer than LZ_F2_CAP hits (repeats) are taken in pieces; seeds with more than 16 probes in groups of 16.
+// k_scan_hits2 (the fused path, below) repeats steps 1 and 2 line for line with its own CAP -- as one pair of shared functions the
+// marks of step 2 compiled to predicated stores instead of branches and the kernel ran 1.5 % slower (profiles/seed_dedup_ab_series.json):
+// a change to either copy goes into both.
 #ifndef LZ_F2_CAP
-#define LZ_F2_CAP   2560                             // hits per piece of a wave's concatenation: a multiple of 512; own[] 5 KiB + 4.5 KiB of tables per wave = four workgroups per CU (the 64 positions of a wave have 2.5 k hits on the 50 Mbp pair)
+#define LZ_F2_CAP   2560                             // k_fill_hits2's CAP: own[] 5 KiB + 4.5 KiB of tables per wave = four workgroups per CU (the 64 positions of a wave have 2.5 k hits on the 50 Mbp pair)
 #endif
-#define LZ_F2_WORDS (LZ_F2_CAP / 2 / 64)             // 32-bit words of own[] per lane
-static_assert(LZ_F2_CAP % 512 == 0, "whole 16-byte groups of own[] per lane");
-struct LzFill2Wave {
-    alignas(16) u32 own32[LZ_F2_CAP / 2];            // own[]: u16 list ids (1 + lane * 16 + probe), 0 = no list starts here
+template <int CAP> struct LzListWave {               // CAP: hits per piece of a wave's concatenation
+    static_assert(CAP % 512 == 0, "whole 16-byte groups of own[] per lane");
+    alignas(16) u32 own32[CAP / 2];                  // own[]: u16 list ids (1 + lane * 16 + probe), 0 = no list starts here
     u32 lsrc[64 * LZ_FILL_GROUP];                    // list -> (first wpos index - start of the list in the concatenation)
     uint2 ent[64];                                   // entry -> (place of its run in the key array - start of the run, pos2)
 };
@@ -523,6 +497,7 @@ __device__ __forceinline__ u32 lz_dpp_u32(u32 ident, u32 src) { return (u32)__bu
     v = OP(lz_dpp_u32<0x143, 0xc, 0xf>(0u, v), v);
 __device__ __forceinline__ u32 lz_uadd(u32 a, u32 b) { return a + b; }
 __device__ __forceinline__ u32 lz_umax(u32 a, u32 b) { return a > b ? a : b; }
+#define LZ_F2_WORDS (LZ_F2_CAP / 2 / 64)             // 32-bit words of own[] per lane
 // SELF: a self-comparison (lz_common.hpp, LzSelfDev): step 1 clips every list to the hits that survive, before the
 // wave scan (k_count_sorted_self counted the same); the rest of the kernel is the same code.
 template <bool SELF>
@@ -532,8 +507,8 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
              const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, const u64* __restrict__ off,
              u64 base, u64* __restrict__ keys, LzSelfDev self)
 {
-    __shared__ LzFill2Wave shw[LZ_TPB / 64];
-    LzFill2Wave& sh = shw[threadIdx.x >> 6];
+    __shared__ LzListWave<LZ_F2_CAP> shw[LZ_TPB / 64];
+    LzListWave<LZ_F2_CAP>& sh = shw[threadIdx.x >> 6];
     unsigned short* const own = reinterpret_cast<unsigned short*>(sh.own32);
     const u32 lane = threadIdx.x & 63u;
     const u32 j = blockIdx.x * LZ_TPB + threadIdx.x;           // one sorted entry per lane (sk / sv: the chunk's range of the list)
@@ -637,33 +612,31 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
     }
 }
 
+// the chunk's positions [i0, i1) lie in blocks i0 >> shift .. (i1 - 1) >> shift: a contiguous range of the sorted list
+static void lz_chunk_range(const LzCtx& c, u32 i0, u32 i1, const u32*& sk, const u32*& sv, u32& n)
+{
+    if (c.blk_start_host.empty()) return;
+    const u32 b0 = i0 >> c.blk_shift, b1 = (i1 - 1) >> c.blk_shift;
+    const u64 j0 = c.blk_start_host[b0], j1 = c.blk_start_host[std::min<u32>(b1 + 1, c.blk_count)];
+    sk += j0; sv += j0; n = (u32)(j1 - j0);
+}
+
 int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64* keys, hipStream_t st)
 {
     if (n == 0 || i1 <= i0) return 0;
-    // the chunk's positions [i0, i1) lie in blocks i0 >> shift .. (i1 - 1) >> shift: a contiguous range of the sorted list
-    if (!c.blk_start_host.empty()) {
-        const u32 b0 = i0 >> c.blk_shift, b1 = (i1 - 1) >> c.blk_shift;
-        const u64 j0 = c.blk_start_host[b0], j1 = c.blk_start_host[std::min<u32>(b1 + 1, c.blk_count)];
-        sk += j0; sv += j0; n = (u32)(j1 - j0);
-        if (n == 0) return 0;
-    }
+    lz_chunk_range(c, i0, i1, sk, sv, n);
+    if (n == 0) return 0;
+    const dim3 grid((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB));
     c.timer.begin("k_fill_hits", st);
-    if (c.self.mode != LZ_SELF_OFF) {
-        // (lzgpu_seed_hit_search_self declines bucket owners and LZGPU_FILL_SHUFFLE: only this kernel clips)
-        hipLaunchKernelGGL(k_fill_hits2<true>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
+    if (c.self.mode != LZ_SELF_OFF)                             // (lzgpu_seed_hit_search_self declines bucket owners: only k_fill_hits2 clips)
+        hipLaunchKernelGGL(k_fill_hits2<true>, grid, dim3(LZ_TPB), 0, st,
                            lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, c.self);
-    } else if (c.n_owners > 1)
-        hipLaunchKernelGGL(k_fill_hits<true>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
+    else if (c.n_owners > 1)
+        hipLaunchKernelGGL(k_fill_hits, grid, dim3(LZ_TPB), 0, st,
                            lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, c.n_owners, c.owner);
-    else {
-        static const bool old_fill = getenv("LZGPU_FILL_SHUFFLE") != nullptr;   // A/B aid: round 2's shuffle-search fill
-        if (old_fill)
-            hipLaunchKernelGGL(k_fill_hits<false>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
-                               lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, 1u, 0u);
-        else
-            hipLaunchKernelGGL(k_fill_hits2<false>, dim3((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB)), dim3(LZ_TPB), 0, st,
-                               lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, LzSelfDev{});
-    }
+    else
+        hipLaunchKernelGGL(k_fill_hits2<false>, grid, dim3(LZ_TPB), 0, st,
+                           lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, base, keys, LzSelfDev{});
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;
@@ -835,22 +808,6 @@ int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStrea
     return 0;
 }
 
-// rank of the lane among the lanes of its wave that hold the same 8-bit key (lower lanes first), the size of
-// that group and whether the lane is its last member; lanes with valid == false are in no group
-__device__ __forceinline__ void lz_match8(u32 key, bool valid, u32 lane, u32& rank, u32& count, bool& last)
-{
-    u64 peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = ((key >> b) & 1u) != 0;
-        const u64 m = __ballot(bit && valid);
-        peers &= bit ? m : ~m;
-    }
-    const u64 below = (1ull << lane) - 1ull;
-    rank = (u32)__popcll(peers & below);
-    count = (u32)__popcll(peers);
-    last = (peers >> lane) == 1ull;
-}
 // exclusive prefix sum over the first 256 threads of a workgroup (every thread of the workgroup calls it)
 __device__ __forceinline__ u32 lz_exscan256(u32 v, u32* wtot /*LDS, [4]*/)
 {
@@ -871,8 +828,10 @@ __device__ __forceinline__ u32 lz_exscan256(u32 v, u32* wtot /*LDS, [4]*/)
 //                 flight -- with no barrier and nothing in LDS but the 32 KiB table, so every resident wave is in
 //                 this code all the time.  Output: the 4-byte summary of a hit whose scans both ended; the rare hit
 //                 with a scan that goes on (~3 %) becomes a 64-byte task in a global list (one atomic per wave).
-//   k_scan_tasks  one lane per task: the scans that go on, to their end or the LZ_LUT_MAXWIN cap; full waves.
-//   k_partition   keys + summaries -> records, every tile stably sorted by partition in place (+ the tile tables).
+//   k_scan_tasks  one lane per task: the scans that go on, to their end or the LZ_LUT_MAXWIN cap; full waves.  <MODE, false>
+//                 here; <0, true> behind the fused kernel.
+//   k_partition   <false>: keys + summaries -> records, every tile stably sorted by partition in place (+ the tile
+//                 tables); <true>: the same on the fused kernel's tagged records.
 // (One fused kernel did all of this per tile behind barriers: its workgroups spent half their time in the light
 // phases -- queue drain on two waves, ranks, write-out -- while holding the LDS and the wave slots the scans need.)
 struct LzScanTask { u32 idx; s32 diag; LzLutScan L, R; };
@@ -1039,30 +998,39 @@ k_scan_hits(LzExtendParams P, LzLutParams Q, const u64* __restrict__ keys, u64 n
 #ifndef LZ_ST_TPB
 #define LZ_ST_TPB 512                                // lanes per workgroup of k_scan_tasks: two workgroups share a CU (the tables are 64 KiB of LDS), 16 waves per CU (256: 5.3 ms per step, 512: 4.4, 1024: 4.2)
 #endif
-template <int MODE>
+// TAGGED (MODE 0, the fused path): out takes the whole tagged record, over the provisional one the queued hit left (payload
+// and SLOW flag were missing).  Otherwise the task's hit gets its summary (k_scan_hits left the slot alone).
+template <int MODE, bool TAGGED>
 __global__ void __launch_bounds__(LZ_ST_TPB)
 k_scan_tasks(LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut_g, const s32* __restrict__ score_tab_g, const LzScanTask* __restrict__ tasks,
-             const u32* __restrict__ n_tasks, u32 n_regions, u32 region_cap, u32* __restrict__ summ)
+             const u32* __restrict__ n_tasks, u32 n_regions, u32 region_cap, std::conditional_t<TAGGED, u64, u32>* __restrict__ out)
 {
-    __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
-    __shared__ s32 ctab[MODE == 1 ? LZ_NCLASS * LZ_NCLASS : 1];
-    for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += LZ_ST_TPB) lut[k] = lut_g[k];
-    if (MODE == 1) for (u32 k = threadIdx.x; k < LZ_NCLASS * LZ_NCLASS; k += LZ_ST_TPB) ctab[k] = score_tab_g[k];
-    __syncthreads();
     constexpr bool SP = MODE == 1;
+    static_assert(!(SP && TAGGED), "pos1 is recovered from the windows a scan ran: without special bytes only");
+    __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
+    __shared__ s32 ctab[SP ? LZ_NCLASS * LZ_NCLASS : 1];
+    for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += LZ_ST_TPB) lut[k] = lut_g[k];
+    if (SP) for (u32 k = threadIdx.x; k < LZ_NCLASS * LZ_NCLASS; k += LZ_ST_TPB) ctab[k] = score_tab_g[k];
+    __syncthreads();
     for (u32 region = blockIdx.x; region < n_regions; region += gridDim.x) {
         const u32 nt = n_tasks[region];
         for (u32 k = threadIdx.x; k < nt; k += (u32)LZ_ST_TPB) {
             const LzScanTask t = tasks[(size_t)region * region_cap + k];
             LzLutScan L = t.L, R = t.R;
+            // the hit's pos1 from the task (reading the provisional record back would fetch a line for 8 bytes): a side that goes on
+            // (and a task has one) has moved LZ_LUT_WIN_B bases per window it ran -- without special bytes a scan goes on in no other way
+            u32 pos1 = 0;
+            if constexpr (TAGGED) pos1 = L.alive == 1 ? L.s + (u32)LZ_LUT_WIN_B * L.nwin : R.s - (u32)LZ_LUT_WIN_B * R.nwin;
             while (L.alive == 1 && L.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<false, SP>(Q, lut, t.diag, L, ctab);
             while (R.alive == 1 && R.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<true, SP>(Q, lut, t.diag, R, ctab);
-            LZ_NT_ST(lz_lut_summary(L, R, P.min_score), summ + t.idx);
+            const u32 summ = lz_lut_summary(L, R, P.min_score);
+            if constexpr (TAGGED) out[t.idx] = lz_hit_record_tagged(lz_hit_key(pos1, pos1 - (u32)t.diag), summ);
+            else                  LZ_NT_ST(summ, out + t.idx);
         }
     }
 }
 
-// keys + summaries -> records, every tile sorted by partition where it lies (lz_tile_runs.hpp).  One workgroup per tile;
+// keys + summaries (or tagged records) -> records, every tile sorted by partition where it lies (lz_tile_runs.hpp).  One workgroup per tile;
 // a wave owns 256 consecutive hits (64 per round), so ranks by (wave, round, lane) follow the discovery order.
 struct LzPartShared {
     union alignas(16) {
@@ -1073,34 +1041,6 @@ struct LzPartShared {
     u32 tstart[LZ_NBIN], wtot[4];
 };
 static_assert(LZ_PP_TILE == LZ_PP_TILE_HOST, "lz_tile_runs.hpp addresses runs by the tile size");
-// The lanes of a round that hold the same partition find each other through a 64-bit bitmap in LDS (atomic OR of
-// 1 << lane, one read; the result does not depend on the order of the ORs), which gives rank and count in one pass and
-// leaves the per-wave totals behind -- no separate counting pass, no ballots.  bin = the partition of record k of the lane.
-// Ends behind a barrier with the per-partition counts chained in wave order in wcnt, the tile-local starts in tstart,
-// and the tile's two table rows written.
-#define LZ_PART_RANKS(BIN_OF_)                                                                                         \
-    u32 slot[LZ_PP_ROUNDS];                                                                                            \
-    _Pragma("unroll")                                                                                                  \
-    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {                                                                           \
-        /* (each wave works on its own rows of bm / wcnt: LDS operations of one wave execute in order) */              \
-        const bool valid = l0 + 64u * r < tile_n;                                                                      \
-        const u32 bin = BIN_OF_(r);                                                                                    \
-        if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);                                        \
-        const u64 peers = valid ? sh.bm[w][bin] : 0ull;                                                                \
-        const u32 old = valid ? sh.wcnt[w][bin] : 0u;                                                                  \
-        if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }  /* the highest peer */ \
-        slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));                                                \
-    }                                                                                                                  \
-    __syncthreads();                                                                                                   \
-    u32 tot = 0;                                                                                                       \
-    if (tid < LZ_NBIN) for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }   \
-    const u32 ts = lz_exscan256(tot, sh.wtot);                                                                         \
-    if (tid < LZ_NBIN) {                                                                                               \
-        sh.tstart[tid] = ts;                                                                                           \
-        hist[(size_t)tile * LZ_NBIN + tid] = tot;                                                                      \
-        run_addr[(size_t)tile * LZ_NBIN + tid] = lz_tr_run_addr(tile, ts);                                             \
-    }                                                                                                                  \
-    __syncthreads();
 // the staged tile -> its own place in the record array, tags cleared: 16 bytes per lane, whole lines per wave
 __device__ __forceinline__ void lz_part_store(const u64* stage, u32 tile_n, u64* out /*the tile's first record*/)
 {
@@ -1112,10 +1052,12 @@ __device__ __forceinline__ void lz_part_store(const u64* stage, u32 tile_n, u64*
         else out[k] = v.x;
     }
 }
-// recs may be keys (the sort is in place then): every record of the tile is in registers before the first store, and no
-// other workgroup touches the tile
+// TAGGED: recs holds tagged records (the fused path: the partition rides in bits 55..62); otherwise keys, whose summaries
+// are in summ.  Either way the sort is in place: every record of the tile is in registers before the first store, and no
+// other workgroup touches the tile.
+template <bool TAGGED>
 __global__ void __launch_bounds__(LZ_PP_TPB)
-k_partition(const u64* keys, const u32* __restrict__ summ, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr, u64* recs)
+k_partition(u64* recs, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr, const u32* __restrict__ summ)
 {
     __shared__ LzPartShared sh;
     const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
@@ -1128,33 +1070,69 @@ k_partition(const u64* keys, const u32* __restrict__ summ, u64 n, u32* __restric
 #pragma unroll
     for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
         const bool v = l0 + 64u * r < tile_n;
-        kk[r] = v ? keys[base + l0 + 64u * r] : 0ull;             // (plain loads and stores here: non-temporal ones made this kernel 10-15 % slower)
-        ss[r] = v ? summ[base + l0 + 64u * r] : 0u;
+        kk[r] = v ? recs[base + l0 + 64u * r] : 0ull;             // (plain loads and stores here: non-temporal ones made this kernel 10-15 % slower)
+        if (!TAGGED) ss[r] = v ? summ[base + l0 + 64u * r] : 0u;
     }
     __syncthreads();
-#define LZ_PART_BIN(r_) LZ_KEY_BIN(kk[r_])
-    LZ_PART_RANKS(LZ_PART_BIN)
-#undef LZ_PART_BIN
+    // The lanes of a round that hold the same partition find each other through a 64-bit bitmap in LDS (atomic OR of
+    // 1 << lane, one read; the result does not depend on the order of the ORs), which gives rank and count in one pass and
+    // leaves the per-wave totals behind -- no separate counting pass, no ballots.
+    u32 slot[LZ_PP_ROUNDS];
+#pragma unroll
+    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
+        // (each wave works on its own rows of bm / wcnt: LDS operations of one wave execute in order)
+        const bool valid = l0 + 64u * r < tile_n;
+        const u32 bin = TAGGED ? LZ_REC_TAG(kk[r]) : LZ_KEY_BIN(kk[r]);
+        if (valid) atomicOr((unsigned long long*)&sh.bm[w][bin], 1ull << lane);
+        const u64 peers = valid ? sh.bm[w][bin] : 0ull;
+        const u32 old = valid ? sh.wcnt[w][bin] : 0u;
+        if (valid && (peers >> lane) == 1ull) { sh.wcnt[w][bin] = old + (u32)__popcll(peers); sh.bm[w][bin] = 0ull; }  // the highest peer
+        slot[r] = old + (u32)__popcll(peers & ((1ull << lane) - 1ull));
+    }
+    __syncthreads();
+    // the per-partition counts chained in wave order in wcnt, the tile-local starts in tstart, the tile's two table rows
+    u32 tot = 0;
+    if (tid < LZ_NBIN) for (u32 k = 0; k < LZ_PP_WAVES; k++) { const u32 v = sh.wcnt[k][tid]; sh.wcnt[k][tid] = tot; tot += v; }
+    const u32 ts = lz_exscan256(tot, sh.wtot);
+    if (tid < LZ_NBIN) {
+        sh.tstart[tid] = ts;
+        hist[(size_t)tile * LZ_NBIN + tid] = tot;
+        run_addr[(size_t)tile * LZ_NBIN + tid] = lz_tr_run_addr(tile, ts);
+    }
+    __syncthreads();
     // every record gets its place: rank among the same-partition lanes of its wave's round, on top of the wave's
     // running offset (stable: lanes, rounds and waves all follow the discovery order)
 #pragma unroll
     for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
-        const u32 bin = LZ_KEY_BIN(kk[r]);
-        if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = lz_hit_record(kk[r], ss[r]);
+        const u32 bin = TAGGED ? LZ_REC_TAG(kk[r]) : LZ_KEY_BIN(kk[r]);
+        if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = TAGGED ? kk[r] : lz_hit_record(kk[r], ss[r]);
     }
     __syncthreads();
     lz_part_store(sh.stage, tile_n, recs + base);
 }
 
-// grid of k_scan_hits for n hits, and the geometry of its task list: one region per wave, room for 1/32 of the
-// wave's hits + 64 (64 B each; the usual load is ~3 %); a hit that finds its region full is left to phase B
 static int lz_scan_tpb(int mode)
 {
     static const int env = getenv("LZGPU_SC_TPB") ? atoi(getenv("LZGPU_SC_TPB")) : 0;      // A/B aid: 512, 640, 768 or 1024
     if (mode != 0) return LZ_SC_TPB;
     return (env == 512 || env == 640 || env == 768 || env == 1024) ? env : 640;     // 640: five waves per SIMD at 89 VGPRs (512: 72.5, 640: 69.7, 768 with 8 spilled registers: 75.9 ms per step)
 }
-static void lz_scan_geometry(LzCtx& c, int mode, u64 n, u32& grid, u32& n_regions, u32& region_cap)
+// The task list of a set for n hits scanned by n_regions waves (k_scan_hits in `mode`, or k_scan_hits2 as mode 0): one region
+// per wave, room for 1/32 of the wave's hits + 64; a hit that finds its region full is left to phase B.
+// (64 B each; ~3 % of the hits become tasks on plain sequences: 1/32 of them fit, 2 GiB less to allocate than with 1/8.
+// With special bytes that do not end a scan -- IUPAC codes -- every window that meets one goes on as a task as well:
+// 1/12, or the overflow lands on phase B's slow path: 1 % of the hits there took k_settle2 from 20 to 84 ms.)
+static int lz_task_regions(LzCtx& c, int set, int mode, u64 n, u32 n_regions, u32& region_cap)
+{
+    region_cap = (u32)std::min<u64>(n / (mode == 1 ? 12 : 32) / n_regions + 64, 1u << 20);
+    static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook: tiny regions, so that hits find theirs full
+    if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
+    int rc;
+    if (mode < 2 && (rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
+    return c.scan_ntasks[set].ensure((size_t)n_regions * 4);
+}
+// grid of k_scan_hits for n hits, and the set's summaries and task list
+static int lz_scan_buffers(LzCtx& c, int set, int mode, u64 n, u32& grid, u32& n_regions, u32& region_cap)
 {
     const u32 wpg = (u32)lz_scan_tpb(mode) / 64u;
     int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
@@ -1162,22 +1140,15 @@ static void lz_scan_geometry(LzCtx& c, int mode, u64 n, u32& grid, u32& n_region
     const u64 nspans = (n + 64u * LZ_SC_ROUNDS - 1) / (64u * LZ_SC_ROUNDS), want = (nspans + wpg - 1) / wpg;
     grid = (u32)std::min<u64>(want ? want : 1, (u64)wgs * (u64)cus);
     n_regions = grid * wpg;
-    // (64 B each; ~3 % of the hits become tasks on plain sequences: 1/32 of them fit, 2 GiB less to allocate than with 1/8.
-    // With special bytes that do not end a scan -- IUPAC codes -- every window that meets one goes on as a task as well:
-    // 1/12, or the overflow lands on phase B's slow path: 1 % of the hits there took k_settle2 from 20 to 84 ms.)
-    region_cap = (u32)std::min<u64>(n / (mode == 1 ? 12 : 32) / n_regions + 64, 1u << 20);
-    static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook: tiny regions, so that hits find theirs full
-    if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
+    const int rc = c.summ[set].ensure((size_t)n * 4);
+    return rc ? rc : lz_task_regions(c, set, mode, n, n_regions, region_cap);
 }
 // buffers of a set for chunks of up to max_n hits (sized once per search: chunk sizes differ a little, and a
 // device buffer that grows is freed and allocated again)
 int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n)
 {
-    u32 grid, n_regions, region_cap; int rc;
-    lz_scan_geometry(c, mode, max_n, grid, n_regions, region_cap);
-    if ((rc = c.summ[set].ensure((size_t)max_n * 4))) return rc;
-    if (mode < 2 && (rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
-    return c.scan_ntasks[set].ensure((size_t)n_regions * 4);
+    u32 grid, n_regions, region_cap;
+    return lz_scan_buffers(c, set, mode, max_n, grid, n_regions, region_cap);
 }
 
 int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
@@ -1187,10 +1158,7 @@ int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const Lz
     int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
     int rc;
     u32 grid, n_regions, task_cap;
-    lz_scan_geometry(c, mode, n, grid, n_regions, task_cap);
-    if ((rc = c.summ[set].ensure((size_t)n * 4))) return rc;
-    if (mode < 2 && (rc = c.scan_tasks[set].ensure((size_t)n_regions * task_cap * sizeof(LzScanTask)))) return rc;
-    if ((rc = c.scan_ntasks[set].ensure((size_t)n_regions * 4))) return rc;
+    if ((rc = lz_scan_buffers(c, set, mode, n, grid, n_regions, task_cap))) return rc;
     u32* summ = c.summ[set].as<u32>(); LzScanTask* tasks = c.scan_tasks[set].as<LzScanTask>(); u32* ntk = c.scan_ntasks[set].as<u32>();
     c.timer.begin("k_scan_hits", st);
     const int tpb = lz_scan_tpb(mode);
@@ -1207,21 +1175,25 @@ int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const Lz
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     if (mode < 2) {
+        const dim3 tgrid(std::min<u32>(n_regions, 4u * (u32)cus));
         c.timer.begin("k_scan_tasks", st);
-        if (mode == 0) hipLaunchKernelGGL(k_scan_tasks<0>, dim3(std::min<u32>(n_regions, 4u * (u32)cus)), dim3(LZ_ST_TPB), 0, st, P, Q, lut, score_tab, tasks, ntk, n_regions, task_cap, summ);
-        else           hipLaunchKernelGGL(k_scan_tasks<1>, dim3(std::min<u32>(n_regions, 4u * (u32)cus)), dim3(LZ_ST_TPB), 0, st, P, Q, lut, score_tab, tasks, ntk, n_regions, task_cap, summ);
+        if (mode == 0) hipLaunchKernelGGL((k_scan_tasks<0, false>), tgrid, dim3(LZ_ST_TPB), 0, st, P, Q, lut, score_tab, tasks, ntk, n_regions, task_cap, summ);
+        else           hipLaunchKernelGGL((k_scan_tasks<1, false>), tgrid, dim3(LZ_ST_TPB), 0, st, P, Q, lut, score_tab, tasks, ntk, n_regions, task_cap, summ);
         c.timer.end(st);
         LZ_HIP(hipGetLastError());
     }
     return 0;
 }
 
-int lzk_partition(LzCtx& c, int set, u64* keys, u64 n, u32* hist, u32* run_addr, hipStream_t st)
+// tagged: recs are the fused path's tagged records (summ is not read); otherwise keys, with their summaries in summ
+int lzk_partition(LzCtx& c, bool tagged, u64* recs, const u32* summ, u64 n, u32* hist, u32* run_addr, hipStream_t st)
 {
     if (n == 0) return 0;
     const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
     c.timer.begin("k_partition", st);
-    hipLaunchKernelGGL(k_partition, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, keys, c.summ[set].as<u32>(), n, hist, run_addr, keys);
+    if (!tagged && !summ) return LZGPU_ERR_ARG;
+    if (!tagged) hipLaunchKernelGGL(k_partition<false>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, recs, n, hist, run_addr, summ);
+    else         hipLaunchKernelGGL(k_partition<true>, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, recs, n, hist, run_addr, summ);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;
@@ -1229,15 +1201,15 @@ int lzk_partition(LzCtx& c, int set, u64* keys, u64 n, u32* hist, u32* run_addr,
 
 // ------------------------------------------------------------------------------------------
 // The fused path of scan mode 0: hit enumeration and phase A in one kernel, over a context-inlined table.
-//   k_build_wctx   wctx[e] = the 32 bytes of the target's 2-bit array that hold both first windows of pos1 = wpos[e]
-//                  (lz_lut.hpp, lz_wctx_make): k_scan_hits gathers one random 64-byte line per hit for these; here they sit
-//                  beside the table entry and are read where k_fill_hits2 reads wpos[] -- in ascending runs, one per list.
-//   k_scan_hits2   k_fill_hits2's steps 1-2 (the same code), then per hit: wpos[e] + wctx[e] + the query windows (which depend
-//                  on pos2 alone: one line per entry), lz_scan_round<false>, ONE tagged 8-byte record at the hit's place in
-//                  discovery order.  No keys, no summaries, no partition bytes.  Persistent waves (the 64 KiB tables are
-//                  loaded once per workgroup) that stride over the 64-entry groups of the sorted list.
-//   k_scan_tasks2  replaces the provisional record a queued hit left (payload and SLOW flag were missing).
-//   k_partition2   sorts the tagged records in place (the partition rides in bits 55..62).
+//   k_build_wctx          wctx[e] = the 32 bytes of the target's 2-bit array that hold both first windows of pos1 = wpos[e]
+//                         (lz_lut.hpp, lz_wctx_make): k_scan_hits gathers one random 64-byte line per hit for these; here they sit
+//                         beside the table entry and are read where k_fill_hits2 reads wpos[] -- in ascending runs, one per list.
+//   k_scan_hits2          k_fill_hits2's steps 1-2 (the same code), then per hit: wpos[e] + wctx[e] + the query windows
+//                         (which depend on pos2 alone: one line per entry), lz_scan_round<false>, ONE tagged 8-byte record at the
+//                         hit's place in discovery order.  No keys, no summaries, no partition bytes.  Persistent waves (the
+//                         64 KiB tables are loaded once per workgroup) that stride over the 64-entry groups of the sorted list.
+//   k_scan_tasks<0, true> replaces the provisional record a queued hit left.
+//   k_partition<true>     sorts the tagged records in place.
 __global__ void __launch_bounds__(LZ_TPB)
 k_build_wctx(const u32* __restrict__ wpos, u64 num_words, const u8* __restrict__ two, LzVec16* __restrict__ wctx)
 {
@@ -1247,11 +1219,6 @@ k_build_wctx(const u32* __restrict__ wpos, u64 num_words, const u8* __restrict__
     wctx[j] = lz_load16(two + lz_wctx_first_byte(pos1) + 16u * (u32)(j & 1u));
 }
 
-template <int CAP> struct LzFuse2Wave {
-    alignas(16) u32 own32[CAP / 2];                  // as LzFill2Wave
-    u32 lsrc[64 * LZ_FILL_GROUP];
-    uint2 ent[64];
-};
 // the loads of one trip of 64 hits (issued a trip ahead of the arithmetic)
 struct LzFuseTrip { u32 p1, pos2, dst; bool ok; LzWctx cx; LzVec16 ql, qr; };
 
@@ -1263,13 +1230,12 @@ k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
              LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut_g,
              u64* __restrict__ recs, LzScanTask* __restrict__ tasks, u32* __restrict__ n_tasks, u32 region_cap, LzSelfDev self)
 {
-    static_assert(CAP % 512 == 0, "whole 16-byte groups of own[] per lane");
-    constexpr int WORDS = CAP / 2 / 64;
     __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
-    __shared__ LzFuse2Wave<CAP> shw[TPB / 64];
+    constexpr int WORDS = CAP / 2 / 64;
+    __shared__ LzListWave<CAP> shw[TPB / 64];
     for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += TPB) lut[k] = lut_g[k];
     __syncthreads();
-    LzFuse2Wave<CAP>& sh = shw[threadIdx.x >> 6];
+    LzListWave<CAP>& sh = shw[threadIdx.x >> 6];
     unsigned short* const own = reinterpret_cast<unsigned short*>(sh.own32);
     const u32 lane = threadIdx.x & 63u;
     const u32 region = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6), nwaves = gridDim.x * (TPB / 64);
@@ -1373,7 +1339,7 @@ k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
                     rl.qv = t.ql; rr.qv = t.qr;
                     u32 summ;
                     lz_scan_round<false>(P, Q, lut, nullptr, key, t.ok, rl, rr, t.dst, lane, summ, my_tasks, my_n, region_cap);
-                    // (a queued hit: summ == 0, the provisional record k_scan_tasks2 completes)
+                    // (a queued hit: summ == 0, the provisional record k_scan_tasks completes)
                     if (t.ok) LZ_NT_ST(lz_hit_record_tagged(key, summ), recs + t.dst);
                 };
                 LzFuseTrip ta, tb2;
@@ -1395,55 +1361,6 @@ k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
     if (lane == 0) n_tasks[region] = my_n < region_cap ? my_n : region_cap;
 }
 
-__global__ void __launch_bounds__(LZ_ST_TPB)
-k_scan_tasks2(LzExtendParams P, LzLutParams Q, const LzLutEntry* __restrict__ lut_g, const LzScanTask* __restrict__ tasks,
-              const u32* __restrict__ n_tasks, u32 n_regions, u32 region_cap, u64* __restrict__ recs)
-{
-    __shared__ LzLutEntry lut[LZ_LUT_TOTAL];
-    for (u32 k = threadIdx.x; k < LZ_LUT_TOTAL; k += LZ_ST_TPB) lut[k] = lut_g[k];
-    __syncthreads();
-    for (u32 region = blockIdx.x; region < n_regions; region += gridDim.x) {
-        const u32 nt = n_tasks[region];
-        for (u32 k = threadIdx.x; k < nt; k += (u32)LZ_ST_TPB) {
-            const LzScanTask t = tasks[(size_t)region * region_cap + k];
-            LzLutScan L = t.L, R = t.R;
-            // the hit's pos1 from the task (reading the provisional record back would fetch a line for 8 bytes): a side that goes on
-            // (and a task has one) has moved LZ_LUT_WIN_B bases per window it ran -- without special bytes a scan goes on in no other way
-            const u32 pos1 = L.alive == 1 ? L.s + (u32)LZ_LUT_WIN_B * L.nwin : R.s - (u32)LZ_LUT_WIN_B * R.nwin;
-            while (L.alive == 1 && L.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<false, false>(Q, lut, t.diag, L, nullptr);
-            while (R.alive == 1 && R.nwin < (u32)LZ_LUT_MAXWIN) lz_lut_step<true, false>(Q, lut, t.diag, R, nullptr);
-            recs[t.idx] = lz_hit_record_tagged(lz_hit_key(pos1, pos1 - (u32)t.diag), lz_lut_summary(L, R, P.min_score));
-        }
-    }
-}
-
-// k_partition on tagged records, in place
-__global__ void __launch_bounds__(LZ_PP_TPB)
-k_partition2(u64* recs, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr)
-{
-    __shared__ LzPartShared sh;
-    const u32 tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-    const u32 tile = blockIdx.x;
-    const u64 base = (u64)tile * LZ_PP_TILE;
-    const u32 tile_n = (n - base < (u64)LZ_PP_TILE) ? (u32)(n - base) : (u32)LZ_PP_TILE;
-    for (u32 k = tid; k < LZ_PP_WAVES * LZ_NBIN; k += LZ_PP_TPB) { (&sh.wcnt[0][0])[k] = 0; (&sh.bm[0][0])[k] = 0ull; }
-    const u32 l0 = w * (64u * LZ_PP_ROUNDS) + lane;
-    u64 rr[LZ_PP_ROUNDS];
-#pragma unroll
-    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) rr[r] = (l0 + 64u * r < tile_n) ? recs[base + l0 + 64u * r] : 0ull;
-    __syncthreads();
-#define LZ_PART_BIN(r_) LZ_REC_TAG(rr[r_])
-    LZ_PART_RANKS(LZ_PART_BIN)
-#undef LZ_PART_BIN
-#pragma unroll
-    for (u32 r = 0; r < LZ_PP_ROUNDS; r++) {
-        const u32 bin = LZ_REC_TAG(rr[r]);
-        if (l0 + 64u * r < tile_n) sh.stage[sh.tstart[bin] + sh.wcnt[w][bin] + slot[r]] = rr[r];
-    }
-    __syncthreads();
-    lz_part_store(sh.stage, tile_n, recs + base);
-}
-
 int lzk_wctx_build(LzCtx& c)
 {
     const u64 nw = c.num_words;
@@ -1456,7 +1373,6 @@ int lzk_wctx_build(LzCtx& c)
     return 0;
 }
 
-// the fused kernel's grid (one workgroup per CU: its LDS) and the task regions of its waves
 // LDS: the tables + a wave's own[] of CAP cells and 4.5 KiB of lists: 8 waves x 2560 cells, 12 x 1024 or 16 x 512 in 160 KiB.
 // The kernel is bound by the latency of the scans' dependent table look-ups, which only other waves hide: 84.5, 67.9, 61.6 ms per
 // step on the 50 Mbp pair with 8, 12, 16 waves (121 VGPRs: four waves per SIMD), however short the pieces get.  A
@@ -1467,37 +1383,28 @@ static u32 lz_fused_tpb(LzCtx& c)
     if (c.self.mode != LZ_SELF_OFF) return 512u;
     return (env == 512 || env == 768 || env == 1024) ? (u32)env : 1024u;
 }
-static void lz_fused_geometry(LzCtx& c, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
+// the fused kernel's grid (one workgroup per CU: its LDS) and the set's task list
+static int lz_fused_buffers(LzCtx& c, int set, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
 {
     int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
     grid = (u32)cus; n_regions = grid * (lz_fused_tpb(c) / 64u);
-    region_cap = (u32)std::min<u64>(n_hits / 32 / n_regions + 64, 1u << 20);
-    static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook (lz_scan_geometry)
-    if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
+    return lz_task_regions(c, set, 0, n_hits, n_regions, region_cap);
 }
 int lzk_fused_reserve(LzCtx& c, int set, u64 max_n)
 {
-    u32 grid, n_regions, region_cap; int rc;
-    lz_fused_geometry(c, max_n, grid, n_regions, region_cap);
-    if ((rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
-    return c.scan_ntasks[set].ensure((size_t)n_regions * 4);
+    u32 grid, n_regions, region_cap;
+    return lz_fused_buffers(c, set, max_n, grid, n_regions, region_cap);
 }
 // lzk_fill_hits + lzk_scan_hits of mode 0 in one launch: the chunk's hits as tagged records, in discovery order
 int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
                    const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st)
 {
     if (n == 0 || i1 <= i0 || n_hits == 0) return 0;
-    if (!c.blk_start_host.empty()) {                            // (lzk_fill_hits: the chunk's range of the sorted list)
-        const u32 b0 = i0 >> c.blk_shift, b1 = (i1 - 1) >> c.blk_shift;
-        const u64 j0 = c.blk_start_host[b0], j1 = c.blk_start_host[std::min<u32>(b1 + 1, c.blk_count)];
-        sk += j0; sv += j0; n = (u32)(j1 - j0);
-        if (n == 0) return 0;
-    }
+    lz_chunk_range(c, i0, i1, sk, sv, n);
+    if (n == 0) return 0;
     int rc;
     u32 grid, n_regions, region_cap;
-    lz_fused_geometry(c, n_hits, grid, n_regions, region_cap);
-    if ((rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
-    if ((rc = c.scan_ntasks[set].ensure((size_t)n_regions * 4))) return rc;
+    if ((rc = lz_fused_buffers(c, set, n_hits, grid, n_regions, region_cap))) return rc;
     LzScanTask* tasks = c.scan_tasks[set].as<LzScanTask>(); u32* ntk = c.scan_ntasks[set].as<u32>();
     c.timer.begin("k_scan_hits", st);
     const u32 tpb = lz_fused_tpb(c);
@@ -1511,17 +1418,7 @@ int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, con
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     c.timer.begin("k_scan_tasks", st);
-    hipLaunchKernelGGL(k_scan_tasks2, dim3(std::min<u32>(n_regions, 4u * grid)), dim3(LZ_ST_TPB), 0, st, P, Q, lut, tasks, ntk, n_regions, region_cap, tagged);
-    c.timer.end(st);
-    LZ_HIP(hipGetLastError());
-    return 0;
-}
-int lzk_partition_tagged(LzCtx& c, u64* tagged, u64 n, u32* hist, u32* run_addr, hipStream_t st)
-{
-    if (n == 0) return 0;
-    const u32 ntiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
-    c.timer.begin("k_partition", st);
-    hipLaunchKernelGGL(k_partition2, dim3(ntiles), dim3(LZ_PP_TPB), 0, st, tagged, n, hist, run_addr);
+    hipLaunchKernelGGL((k_scan_tasks<0, true>), dim3(std::min<u32>(n_regions, 4u * grid)), dim3(LZ_ST_TPB), 0, st, P, Q, lut, (const s32*)nullptr, tasks, ntk, n_regions, region_cap, tagged);
     c.timer.end(st);
     LZ_HIP(hipGetLastError());
     return 0;

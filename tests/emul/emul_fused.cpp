@@ -18,7 +18,7 @@ extern "C" void emul_wctx_windows(const u8* two, const u32* pos1, u32 n, u8* ent
     }
 }
 
-// tagged[k] = the record k_scan_hits2 stores, plain[k] = lz_hit_record, tag[k] / untagged[k] = what k_hist2 / k_partition2 make of it
+// tagged[k] = the record k_scan_hits2 stores, plain[k] = lz_hit_record, tag[k] / untagged[k] = what k_hist2 / k_partition<true> make of it
 extern "C" void emul_tagged_records(const u64* key, const u32* summ, u32 n, u64* tagged, u64* plain, u32* tag, u64* untagged)
 {
     for (u32 k = 0; k < n; k++) {

@@ -1,4 +1,4 @@
-"""Hit tiles sorted by partition in place and phase B gathering its runs (k_partition / k_partition2 -> k_hist_scan ->
+"""Hit tiles sorted by partition in place and phase B gathering its runs (k_partition<false> / k_partition<true> -> k_hist_scan ->
 k_settle2, lastz_amd/csrc/lz_tile_runs.hpp) against the oracle: HSP arrays of both strands and the four counters, on
 
   small    a 3 kbp x 3 kbp pair: one partial tile
