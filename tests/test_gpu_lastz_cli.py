@@ -266,3 +266,19 @@ def test_identical_partitions(sandbox, case):
         assert err.count("[lzgpu] gapped: " + how) >= n, err[-1500:]
     if "declined, reference path" not in notes:
         assert "[lzgpu] gapped: declined" not in err
+
+
+@needs_bins
+def test_another_score_matrix_stays_on_the_gpu(sandbox):
+    """--scores=<file> with a strand-symmetric matrix that is not symmetric (tests/scorings.py: `eight`, every one of the eight
+    classes of the look-up tables' index distinct), explicit x-drop, thresholds and gap penalties: inside the fast path of
+    DESIGN.md 1, so both stages run on the GPU, and the bytes are the pristine binary's"""
+    t, q = seqio.synth_pair(300_000, 250_000, seed=5, block_min=300, block_max=3000)
+    seqio.write_fasta(sandbox / "ts.fa", [("target", t)]); seqio.write_fasta(sandbox / "qs.fa", [("query", q)])
+    args = ["ts.fa", "qs.fa", "--scores=" + os.path.join(H.GOLDEN, "scorings_eight.q"), "--xdrop=910", "--hspthresh=3000", "--gap=400,30",
+            "--ydrop=9400", "--gappedthresh=3000", "--format=maf"]
+    a, err = run(GPU_BIN, args, sandbox, {"LZGPU_VERBOSE": "1"})
+    b, _ = run(REF_BIN, args, sandbox)
+    assert "[lzgpu] search: done on the GPU" in err and "[lzgpu] gapped: done on the GPU" in err and "declined" not in err, err[-1500:]
+    strip = lambda s: "\n".join(l for l in s.split("\n") if not l.startswith("#"))
+    assert strip(a) == strip(b) and a.count("\na score=") > 20
