@@ -102,6 +102,19 @@ int lzo_seed_hit_search(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
                         int32_t hsp_threshold, int entropic, int mode,
                         uint32_t diag_hash_size,
                         lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats);
+/* lastz --self (selfCompare): drops the raw hits the reference drops in find_table_matches, before the processor
+ * and before "raw seed hits" is counted (src/seed_search.c:841-848, 865; seed_hit_below_diagonal, :2052-2235).
+ * same_strand: seq2 is seq1 itself, not its reverse complement (:373).  band: --band, same strand only (:845).
+ * sep1 / sep2: the sepBefore of every partition of a [multi] sequence plus the final NUL; n = 0 when it has none. */
+int lzo_seed_hit_search_self(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
+                             const uint8_t* q, uint32_t qlen, uint32_t start, uint32_t end,
+                             const int8_t* char_to_bits, const lzo_seed* sd,
+                             const int32_t* masked_sub, int32_t xdrop,
+                             int32_t hsp_threshold, int entropic, int mode,
+                             uint32_t diag_hash_size,
+                             int same_strand, uint32_t band,
+                             const uint32_t* sep1, uint32_t n_sep1, const uint32_t* sep2, uint32_t n_sep2,
+                             lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats);
 void lzo_free(void* p);
 
 /* ---- gapped stage (src/gapped_extend.c) ---- */

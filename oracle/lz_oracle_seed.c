@@ -8,6 +8,7 @@
  *   - position table build                src/pos_table.c:144-196,396-476,1042-1110,1326-1344
  *   - seed hit search                     src/seed_search.c:322-574 (private_hit_search)
  *   - table walk                          src/seed_search.c:810-875 (find_table_matches)
+ *   - self-comparison filter and band     src/seed_search.c:373, 841-848, 903-908, 2052-2235
  *   - simple-hit processor + diag hash    src/seed_search.c:1056-1192, src/diag_hash.h:61-101
  *   - x-drop ungapped extension           src/seed_search.c:2528-2959
  * Sequential, single-threaded, deliberately naive: this is the checker.
@@ -279,6 +280,12 @@ typedef struct search_ctx {
     uint32_t* diag_end; uint32_t diag_mask;
     lzo_hsp* out; uint64_t n_out, cap_out;
     lzo_search_stats st;
+    /* lastz --self: seq1 and seq2 are the same sequence (src/seed_search.c:242-258, 372-383) */
+    int self_compare, same_strand;
+    uint32_t band;
+    const uint32_t* sep1; uint32_t n_sep1;      /* sepBefore of every partition + the final NUL; n = 0: not partitioned */
+    const uint32_t* sep2; uint32_t n_sep2;
+    int lost;                                   /* a position that is in no partition (the reference dies there) */
 } search_ctx;
 
 static void report(search_ctx* c, uint32_t pos1, uint32_t pos2, uint32_t length, int32_t s)
@@ -350,6 +357,38 @@ static void process_simple_hit(search_ctx* c, uint32_t pos1, uint32_t pos2, uint
     report(c, pos1, pos2, length, sim);
 }
 
+/* lookup_partition (src/sequences.c:6536-6600) finds the partition ix with sepBefore[ix] < pos < sepBefore[ix+1];
+ * the reference bisects, this walks the separators one by one */
+static int partition_of(const uint32_t* sep, uint32_t n_sep, uint32_t pos)
+{
+    for (uint32_t ix = 0; ix + 1 < n_sep; ix++)
+        if (sep[ix] < pos && pos < sep[ix + 1]) return (int)ix;
+    return -1;
+}
+
+/* src/seed_search.c:2182-2237 (seed_hit_below_diagonal); pos1, pos2 are hit END positions */
+static int below_diagonal(search_ctx* c, uint32_t pos1, uint32_t pos2)
+{
+    if (c->same_strand)                                                 /* :2194-2199, notes (2)-(4) */
+        return pos1 >= pos2;
+
+    pos1 -= (uint32_t)c->sd->length;                                    /* :2203-2204: hit starts */
+    pos2 -= (uint32_t)c->sd->length;
+
+    if (c->n_sep2 == 0) {                                               /* :2208-2214, note (5): seq2 counts backwards */
+        pos2 = (c->qlen - 1) - pos2;
+        return pos1 >= pos2;
+    }
+
+    int ix1 = partition_of(c->sep1, c->n_sep1, pos1);                   /* :2220-2224, note (6) */
+    int ix2 = partition_of(c->sep2, c->n_sep2, pos2);
+    if (ix1 < 0 || ix2 < 0) { c->lost = 1; return 1; }
+    if (ix1 != ix2)                                                     /* :2228-2232 */
+        return ix1 >= ix2;
+    pos2 = (c->sep2[ix2] + c->sep2[ix2 + 1]) - pos2;                    /* :2234: sepBefore + sepAfter of the partition */
+    return pos1 >= pos2;
+}
+
 /* src/seed_search.c:810-875 */
 static void find_table_matches(search_ctx* c, uint32_t packed, uint32_t pos2)
 {
@@ -358,21 +397,25 @@ static void find_table_matches(search_ctx* c, uint32_t packed, uint32_t pos2)
     if (pt->last[packed] == 0) return;
     for (uint32_t pos = pt->last[packed]; pos != NO_PREV; pos = pt->prev[pos]) {
         uint32_t pos1 = pt->adj_start + pt->step * pos;
-        c->st.raw_hits++;
+        if (c->self_compare && below_diagonal(c, pos1, pos2)) continue;            /* :841-842 */
+        if (c->same_strand && c->band > 0 && pos2 - pos1 > c->band) continue;      /* :845-846 */
+        c->st.raw_hits++;                                                          /* :865: counted after the drops */
         if (c->mode == LZO_MODE_PLAIN) report(c, pos1, pos2, seed_len, 0);  /* :995-1029 */
         else                           process_simple_hit(c, pos1, pos2, seed_len);
     }
 }
 
-int lzo_seed_hit_search(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
-                        const uint8_t* q, uint32_t qlen, uint32_t start, uint32_t end,
-                        const int8_t* ctb, const lzo_seed* sd,
-                        const int32_t* masked_sub, int32_t xdrop,
-                        int32_t hsp_threshold, int entropic, int mode,
-                        uint32_t diag_hash_size,
-                        lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats)
+static int seed_hit_search(const search_ctx* self_part,     /* the self-comparison fields, all else zero */
+                           const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
+                           const uint8_t* q, uint32_t qlen, uint32_t start, uint32_t end,
+                           const int8_t* ctb, const lzo_seed* sd,
+                           const int32_t* masked_sub, int32_t xdrop,
+                           int32_t hsp_threshold, int entropic, int mode,
+                           uint32_t diag_hash_size,
+                           lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats)
 {
-    search_ctx c; memset(&c, 0, sizeof(c));
+    search_ctx c = *self_part;
+    *out = NULL; *n_out = 0;
     if (end == 0) end = qlen;
     if (end <= start || end > qlen) return -1;
     if (diag_hash_size == 0) diag_hash_size = 65536;                    /* diag_hash.h:56 */
@@ -410,9 +453,42 @@ int lzo_seed_hit_search(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
         }
     }
     free(c.diag_end);
+    if (c.lost) { free(c.out); *out = NULL; *n_out = 0; return -2; }
     *out = c.out; *n_out = c.n_out;
     if (stats) *stats = c.st;
     return 0;
+}
+
+int lzo_seed_hit_search(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
+                        const uint8_t* q, uint32_t qlen, uint32_t start, uint32_t end,
+                        const int8_t* ctb, const lzo_seed* sd,
+                        const int32_t* masked_sub, int32_t xdrop,
+                        int32_t hsp_threshold, int entropic, int mode,
+                        uint32_t diag_hash_size,
+                        lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats)
+{
+    search_ctx c; memset(&c, 0, sizeof(c));
+    return seed_hit_search(&c, t, tlen, pt, q, qlen, start, end, ctb, sd, masked_sub, xdrop, hsp_threshold,
+                           entropic, mode, diag_hash_size, out, n_out, stats);
+}
+
+/* lastz --self: the same search with selfCompare set.  sameStrand is the caller's to say (the reference derives it
+ * from the two sequences' revCompFlags, src/seed_search.c:373); a band is looked at on the same strand only (:845) */
+int lzo_seed_hit_search_self(const uint8_t* t, uint32_t tlen, const lzo_postable* pt,
+                             const uint8_t* q, uint32_t qlen, uint32_t start, uint32_t end,
+                             const int8_t* ctb, const lzo_seed* sd,
+                             const int32_t* masked_sub, int32_t xdrop,
+                             int32_t hsp_threshold, int entropic, int mode,
+                             uint32_t diag_hash_size,
+                             int same_strand, uint32_t band,
+                             const uint32_t* sep1, uint32_t n_sep1, const uint32_t* sep2, uint32_t n_sep2,
+                             lzo_hsp** out, uint64_t* n_out, lzo_search_stats* stats)
+{
+    search_ctx c; memset(&c, 0, sizeof(c));
+    c.self_compare = 1; c.same_strand = same_strand != 0; c.band = band;
+    c.sep1 = sep1; c.n_sep1 = n_sep1; c.sep2 = sep2; c.n_sep2 = n_sep2;
+    return seed_hit_search(&c, t, tlen, pt, q, qlen, start, end, ctb, sd, masked_sub, xdrop, hsp_threshold,
+                           entropic, mode, diag_hash_size, out, n_out, stats);
 }
 
 void lzo_free(void* p) { free(p); }

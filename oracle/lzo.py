@@ -77,6 +77,8 @@ def lib():
                                       C.c_int32, C.c_int, C.c_int, C.c_uint32,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                       C.POINTER(SearchStats)]
+    L.lzo_seed_hit_search_self.argtypes = L.lzo_seed_hit_search.argtypes[:15] + [
+        C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + L.lzo_seed_hit_search.argtypes[15:]
     L.lzo_free.argtypes = [C.c_void_p]
     L.lzo_reduce_to_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.lzo_gapped_extend.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
@@ -159,16 +161,28 @@ class Table:
 
 
 def seed_hit_search(table, q, masked_sub, xdrop=910, hsp_threshold=3000, entropic=True,
-                    mode=0, start=0, end=0, diag_hash_size=65536):
+                    mode=0, start=0, end=0, diag_hash_size=65536, self_strand=None, band=0, sep1=None, sep2=None):
+    """self_strand: None, or lastz --self with q the target itself ("same") or its reverse complement ("opposite");
+    band: --band (same strand only); sep1 / sep2: the separators of a [multi] sequence (sepBefore of every partition
+    plus the final NUL), None without partitions."""
     qa = nul_terminated(q)
     qlen = len(qa) - 1
     out = C.c_void_p()
     n = C.c_uint64()
     st = SearchStats()
-    rc = lib().lzo_seed_hit_search(_ptr(table.t), table.tlen, table.pt, _ptr(qa), qlen, start, end,
-                                   _ptr(table.ctb), C.byref(table.sd), _ptr(masked_sub),
-                                   xdrop, hsp_threshold, int(entropic), mode, diag_hash_size,
-                                   C.byref(out), C.byref(n), C.byref(st))
+    head = (_ptr(table.t), table.tlen, table.pt, _ptr(qa), qlen, start, end,
+            _ptr(table.ctb), C.byref(table.sd), _ptr(masked_sub),
+            xdrop, hsp_threshold, int(entropic), mode, diag_hash_size)
+    if self_strand is None:
+        if band or sep1 is not None or sep2 is not None:
+            raise ValueError("band and separators belong to a self-comparison")
+        rc = lib().lzo_seed_hit_search(*head, C.byref(out), C.byref(n), C.byref(st))
+    else:
+        if self_strand not in ("same", "opposite"):
+            raise ValueError(f"self_strand={self_strand!r}")
+        s1, s2 = (np.ascontiguousarray([] if x is None else x, dtype=np.uint32) for x in (sep1, sep2))
+        rc = lib().lzo_seed_hit_search_self(*head, int(self_strand == "same"), band, _ptr(s1), len(s1), _ptr(s2), len(s2),
+                                            C.byref(out), C.byref(n), C.byref(st))
     if rc != 0:
         raise RuntimeError(f"lzo_seed_hit_search rc={rc}")
     res = np.zeros(n.value, dtype=HSP_DTYPE)
