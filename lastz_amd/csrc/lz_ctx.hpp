@@ -51,17 +51,20 @@ struct SeqSlot {                    // a sequence resident in HBM
     std::vector<u8> host;           // host copy (entropy post-pass needs the raw bytes)
     u8* raw_base()  const { return raw.as<u8>()  + LZ_SEQ_PAD; }
     u8* code_base() const { return code.as<u8>() + LZ_SEQ_PAD; }
+    void release()                  // every DevBuf above (a new one goes in here), and what says they hold something
+    {
+        DevBuf* all[] = { &raw, &code, &dp, &nib, &two, &spc, &two_x, &spc_x, &occ_dev };
+        for (DevBuf* b : all) b->release();
+        have_raw = have_nib = false; code_key = dp_key = 0;
+    }
 };
 
-#define LZ_SETS 3                       // sets of the per-chunk buffers (the chunk pipeline of lzgpu_seed_hit_search)
 struct LzCtx {
     bool inited = false;
     int  device = -1;
     int  num_cus = 256;                 // compute units of the device (MI355X: 256)
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr, stream3 = nullptr;   // chunk pipeline: fill + histogram (stream) | scans (stream3) | partition + phase B (stream2)
     hipStream_t dp_stream = nullptr;    // B3's own stream: lzgpu_gapped_extend(_batch) on one host thread may run beside lzgpu_seed_hit_search on another
-    hipEvent_t ev_keys[LZ_SETS] = {}, ev_summ[LZ_SETS] = {}, ev_part[LZ_SETS] = {}, ev_extended[LZ_SETS] = {}, ev_init = nullptr;
     std::string last_error;
 
     // ---- target + position table (B1)
@@ -88,17 +91,21 @@ struct LzCtx {
     std::vector<u64> blk_start_host;
     u32 blk_shift = 0, blk_count = 1;
     u64* pinned = nullptr; size_t pinned_words = 0;   // host memory the device writes small results into (no staged D2H copies)
-    DevBuf bins[LZ_SETS];           // the partition (high hash byte) of every hit of the chunk, written by the scan kernels of the unfused path
-    DevBuf keys[LZ_SETS];                 // hit keys of a chunk, discovery order (two sets of every per-chunk buffer: the chunk pipeline); on the fused path of scan mode 0
+    DevBuf bins;                    // the partition (high hash byte) of every hit of the chunk, written by the scan kernels of the unfused path
+    DevBuf keys;                          // hit keys of a chunk, discovery order; on the fused path of scan mode 0
                                           // the chunk's tagged records instead (k_scan_hits2), and bins / summ are not allocated.  The partition kernels
                                           // turn it in place into the chunk's records, every tile sorted by partition (lz_tile_runs.hpp): 8 bytes per hit
-    DevBuf bin_base[LZ_SETS];             // the 257 partition offsets (ranks); sets: phase B of a chunk runs while the next chunk is scanned / partitioned
-    DevBuf hist[LZ_SETS], hist_part[LZ_SETS], run_addr[LZ_SETS];   // [tile][partition]: records, then first rank inside the block of 256 tiles; the blocks' first ranks; where the run lies
-    DevBuf summ[LZ_SETS], scan_tasks[LZ_SETS], scan_ntasks[LZ_SETS];   // phase A: 4-byte summary per hit of the chunk; the scans that go on past their first window
+    DevBuf bin_base;                      // the 257 partition offsets (ranks)
+    DevBuf hist, hist_part, run_addr;     // [tile][partition]: records, then first rank inside the block of 256 tiles; the blocks' first ranks; where the run lies
+    DevBuf summ, scan_tasks, scan_ntasks; // phase A: 4-byte summary per hit of the chunk; the scans that go on past their first window
     DevBuf lut;                     // phase-A tables (lz_lut.hpp)
     DevBuf sort_tmp, scan_tmp;
     DevBuf diag_end;                // [LZ_DIAG_SIZE]
     DevBuf score_tab;               // [32*32] s32
+    std::vector<s32> score_sub;     // the 256 x 256 matrix score_tab was made from (empty: none), and its row / column classes:
+    u8 rowc[256] = { 0 }, colc[256] = { 0 };   // the class compression and the upload are skipped while the caller passes the same matrix
+    std::vector<s32> lut_m4; s32 lut_xdrop = -1;   // likewise what lut was built from (empty: not built)
+    DevBuf cls_t, cls_q, cls_tmp;   // the 256-byte class maps on the device: the target's, the query's, B3's (lz_encode_with, dp_stream)
     DevBuf win_tab;                 // the same for lzgpu_window_search (its own: the two callers may use different matrices)
     DevBuf hsp_out, hsp_count;      // candidates + counter
     DevBuf hsp_mc;                  // [n][5]: A/C/G/T match counts of the candidates (entropy inputs) + probe index
@@ -110,13 +117,30 @@ struct LzCtx {
     std::vector<u64> last_order;      // two sort words per HSP of the last search
     int min_scan_mode = 0;            // lzgpu_set_scan_mode
     int last_scan_mode = -1;          // phase-A scan mode of the last search (0/1: look-up tables without/with special masks, 2: byte codes)
-    u64 hit_capacity = (1ull << 31);    // hits per chunk (LZGPU_HIT_CAPACITY): 2^28 -> 2^30 took 10 ms off the 50 Mbp step (fewer launches, fewer passes over the sorted words), 2^30 -> 2^31 another 5.5 (a 50 Mbp strand is one chunk); the buffers follow the largest chunk: 21 bytes per hit, 42 GiB at most
+    u64 hit_capacity = (1ull << 31);    // hits per chunk (LZGPU_HIT_CAPACITY): 2^28 -> 2^30 took 10 ms off the 50 Mbp step (fewer launches, fewer passes over the sorted words), 2^30 -> 2^31 another 5.5 (a 50 Mbp strand is one chunk); the buffers follow the largest chunk: 8.1 bytes per hit on the fused path, 13.1 on the split one, 26 GiB at most
     u64 hsp_capacity = (1ull << 24);
 
     lz_counters counters = {};      // B2 and B3 write disjoint fields (possibly from two host threads); lzgpu_counters copies under counters_m
     std::mutex counters_m;
     KernelTimer timer;              // B1 / B2 launches (the caller's thread)
     KernelTimer dp_timer;           // B3 launches (dp_stream; possibly another host thread)
+
+    // lzgpu_shutdown: EVERY DevBuf declared above (a new member goes in here), the slots' through SeqSlot::release, and what
+    // describes their contents -- nothing outlives the device context it was made on
+    void release_device_memory()
+    {
+        DevBuf* all[] = { &wstart, &wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
+                          &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab,
+                          &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep };
+        for (DevBuf* b : all) b->release();
+        target.release();
+        for (auto& kv : queries) kv.second.release();
+        queries.clear();
+        if (pinned) (void)hipHostFree(pinned);
+        pinned = nullptr; pinned_words = 0;
+        have_table = false; wctx_gen = 0; wctx_code_key = 0;
+        score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
+    }
 };
 
 LzCtx& lz_ctx();
@@ -141,14 +165,14 @@ struct LzLutParams; struct LzLutEntry;
 int lzk_pack2(LzCtx& c, const u8* code_base, const u8* raw_base, u32 len, u8* two, u8* spc, u32 nmask, u32* flags256);
 int lzk_overlap32(LzCtx& c, const u8* src, u8* dst, size_t nblocks);
 int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);      // after the partition of the chunk
-int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n);
-int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
-                  const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ[set], and the partition byte of every hit -> bins
+int lzk_scan_reserve(LzCtx& c, int mode, u64 max_n);
+int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
+                  const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ, and the partition byte of every hit -> bins
 int lzk_partition(LzCtx& c, bool tagged, u64* recs, const u32* summ, u64 n, u32* hist, u32* run_addr, hipStream_t st);   // keys + summaries (or tagged records: summ unused) -> records, in place
 // the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records instead of keys / summaries / partition bytes
 int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
-int lzk_fused_reserve(LzCtx& c, int set, u64 max_n);
-int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
+int lzk_fused_reserve(LzCtx& c, u64 max_n);
+int lzk_scan_fused(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
                    const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st);
 int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, u64 n, const u32* hist, const u32* hist_part, const u32* run_addr,
                const u32* bin_base, u32* diag_end, const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);

@@ -20,7 +20,8 @@
 // ------------------------------------------------------------------------------ context
 
 static LzCtx g_ctx;
-static void lz_release_statics();
+void lz_dp_release_statics();                                  // dp_kernels.hip
+void lz_win_release_statics();                                // window_kernels.hip
 void lz_phase_clocks_print();                                 // seed_kernels.hip (prints only in a -DLZ_PHASE_CLOCKS build)
 LzCtx& lz_ctx() { return g_ctx; }
 
@@ -164,16 +165,7 @@ static int lz_init_locked(int device_index)
     LZ_HIP(hipSetDevice(device_index));
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_index) == hipSuccess && prop.multiProcessorCount > 0) g_ctx.num_cus = prop.multiProcessorCount; }
     LZ_HIP(hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking));
-    LZ_HIP(hipStreamCreateWithFlags(&g_ctx.stream2, hipStreamNonBlocking));
-    LZ_HIP(hipStreamCreateWithFlags(&g_ctx.stream3, hipStreamNonBlocking));
     LZ_HIP(hipStreamCreateWithFlags(&g_ctx.dp_stream, hipStreamNonBlocking));
-    for (int k = 0; k < LZ_SETS; k++) {
-        LZ_HIP(hipEventCreateWithFlags(&g_ctx.ev_keys[k], hipEventDisableTiming));
-        LZ_HIP(hipEventCreateWithFlags(&g_ctx.ev_summ[k], hipEventDisableTiming));
-        LZ_HIP(hipEventCreateWithFlags(&g_ctx.ev_part[k], hipEventDisableTiming));
-        LZ_HIP(hipEventCreateWithFlags(&g_ctx.ev_extended[k], hipEventDisableTiming));
-    }
-    LZ_HIP(hipEventCreateWithFlags(&g_ctx.ev_init, hipEventDisableTiming));
     if (const char* sm = getenv("LZGPU_SCAN_MODE")) { const int v = atoi(sm); if (v >= 0 && v <= 2) g_ctx.min_scan_mode = v; }
     if (const char* hc = getenv("LZGPU_HIT_CAPACITY")) { const long long v = atoll(hc); if (v >= 1024 && v <= (1ll << 31)) g_ctx.hit_capacity = (u64)v; }
     g_ctx.device = device_index;
@@ -213,34 +205,13 @@ extern "C" void lzgpu_shutdown(void)
     (void)hipSetDevice(c.device);
     (void)hipStreamSynchronize(c.stream);
     lz_phase_clocks_print();
-    if (c.stream2) (void)hipStreamSynchronize(c.stream2);
-    if (c.stream3) (void)hipStreamSynchronize(c.stream3);
     if (c.dp_stream) (void)hipStreamSynchronize(c.dp_stream);
     c.timer.resolve(); c.dp_timer.resolve();
-    if (c.pinned) { (void)hipHostFree(c.pinned); c.pinned = nullptr; c.pinned_words = 0; }
-    DevBuf* bufs[] = { &c.target.raw, &c.target.code, &c.wstart, &c.wpos, &c.cnt, &c.off, &c.pk, &c.wiv, &c.wsk, &c.wsv, &c.lut,
-                       &c.sort_tmp, &c.scan_tmp, &c.diag_end, &c.score_tab, &c.hsp_out, &c.hsp_count, &c.hsp_mc,
-                       &c.dev_counters, &c.tb_keys, &c.tb_vals, &c.tb_keys2, &c.tb_vals2, &c.wctx };
-    for (DevBuf* b : bufs) b->release();
-    for (int k = 0; k < LZ_SETS; k++) { DevBuf* sb[] = { &c.bins[k], &c.keys[k], &c.bin_base[k], &c.hist[k], &c.hist_part[k], &c.run_addr[k], &c.summ[k], &c.scan_tasks[k], &c.scan_ntasks[k] }; for (DevBuf* b : sb) b->release(); }
-    for (auto& kv : c.queries) { kv.second.raw.release(); kv.second.code.release(); kv.second.dp.release(); kv.second.nib.release(); kv.second.two.release(); kv.second.spc.release(); kv.second.occ_dev.release(); }
-    c.target.dp.release(); c.target.nib.release(); c.target.two.release(); c.target.spc.release(); c.target.occ_dev.release();
-    c.target.two_x.release(); c.target.spc_x.release();
-    lz_release_statics();
-    c.queries.clear();
+    c.release_device_memory();                                  // (lz_ctx.hpp, beneath the members)
+    lz_dp_release_statics(); lz_win_release_statics();
     (void)hipStreamDestroy(c.stream);
-    if (c.stream2) (void)hipStreamDestroy(c.stream2);
-    if (c.stream3) (void)hipStreamDestroy(c.stream3);
     if (c.dp_stream) (void)hipStreamDestroy(c.dp_stream);
-    c.dp_stream = nullptr;
-    for (int k = 0; k < LZ_SETS; k++) {
-        hipEvent_t* ev[] = { &c.ev_keys[k], &c.ev_summ[k], &c.ev_part[k], &c.ev_extended[k] };
-        for (hipEvent_t* e : ev) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    }
-    if (c.ev_init) (void)hipEventDestroy(c.ev_init);
-    c.ev_init = nullptr; c.stream2 = nullptr; c.stream3 = nullptr;
-    c.stream = nullptr; c.inited = false; c.have_table = false; c.device = -1;
-    c.wctx_gen = 0; c.wctx_code_key = 0;
+    c.stream = nullptr; c.dp_stream = nullptr; c.inited = false; c.device = -1;
     c.n_owners = 1; c.owner = 0; c.last_order.clear();
 }
 
@@ -316,19 +287,15 @@ static int slot_encode(LzCtx& c, SeqSlot& s, const u8 cls[256], DevBuf& cls_dev)
     return 0;
 }
 
-static DevBuf g_cls_t, g_cls_q, g_cls_tmp;
-void lz_dp_release_statics();                                  // dp_kernels.hip
-void lz_win_release_statics();                                // window_kernels.hip
-static void lz_release_statics() { g_cls_t.release(); g_cls_q.release(); g_cls_tmp.release(); lz_dp_release_statics(); lz_win_release_statics(); g_ctx.win_tab.release(); }
 
 // (the two helpers of B3's set-up: on B3's stream, with B3's own class-table buffer and timer)
 int lz_slot_upload_public(LzCtx& c, SeqSlot& s, const u8* bytes, u32 len) { return slot_upload(c, s, bytes, len, false, c.dp_stream); }
 int lz_encode_with(LzCtx& c, const u8* raw, u8* code, u32 len, const u8 cls[256])
 {
-    int rc = g_cls_tmp.ensure(256); if (rc) return rc;
-    LZ_HIP(hipMemcpyAsync(g_cls_tmp.p, cls, 256, hipMemcpyHostToDevice, c.dp_stream));
+    int rc = c.cls_tmp.ensure(256); if (rc) return rc;
+    LZ_HIP(hipMemcpyAsync(c.cls_tmp.p, cls, 256, hipMemcpyHostToDevice, c.dp_stream));
     LZ_HIP(hipStreamSynchronize(c.dp_stream));
-    if ((rc = lzk_encode(c, raw, code, len, g_cls_tmp.as<u8>(), c.dp_stream, &c.dp_timer))) return rc;
+    if ((rc = lzk_encode(c, raw, code, len, c.cls_tmp.as<u8>(), c.dp_stream, &c.dp_timer))) return rc;
     LZ_HIP(hipStreamSynchronize(c.dp_stream));
     return 0;
 }
@@ -369,7 +336,7 @@ extern "C" int lzgpu_table_prepare(const uint8_t* t, uint32_t tlen, uint32_t sta
     memcpy(c.geom.char_to_bits, char_to_bits, 256);
     if ((rc = slot_upload(c, c.target, t, tlen, true))) return rc;
     u8 cls[256]; lzh_make_cls(nullptr, char_to_bits, cls);
-    if ((rc = slot_encode(c, c.target, cls, g_cls_t))) return rc;
+    if ((rc = slot_encode(c, c.target, cls, c.cls_t))) return rc;
     if ((rc = lzk_table_build(c))) return rc;
     c.geom.num_words = c.num_words;
     c.have_table = true;
@@ -499,8 +466,6 @@ struct HostProf {
 };
 static HostProf g_hp;
 
-// the search proper; with c.self.mode != LZ_SELF_OFF the count and fill kernels drop the hits a self-comparison drops
-
 // wctx (lz_ctx.hpp) for the table and the target codes as they are now: rebuilt when either changed since it was
 // built.  It is not to crowd out the per-chunk buffers: when it would take more than half of the device memory that
 // is free (counting what it holds already), or the allocation fails, `fused` comes back false and the search runs
@@ -526,57 +491,102 @@ static int lz_wctx_prepare(LzCtx& c, bool& fused)
     return 0;
 }
 
-static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
+// The query of a search: the caller's bytes, uploaded into the transient slot -1 (not when `upload` is false: the self
+// entry point asks for the length ahead of seed_search, qs stays null), or a resident slot.
+static int lz_search_query(LzCtx& c, const u8* bytes, u32 len, int slot, bool upload, SeqSlot*& qs, u32& qlen)
+{
+    qs = nullptr; qlen = len;
+    if (bytes) {
+        if (!upload) return 0;
+        if (len >= 0x7FFFFFFFu) return LZGPU_NH_SIZE;
+        qs = lz_query_slot(c, -1, true);
+        return slot_upload(c, *qs, bytes, len, false);
+    }
+    qs = slot < 0 ? nullptr : lz_query_slot(c, slot, false);
+    if (!qs) return lz_fail(LZGPU_ERR_ARG, "query slot %d is empty", slot);
+    qlen = qs->len;
+    return 0;
+}
+
+// a result list as the ABI hands it out (lzgpu_free)
+static int lz_hsps_out(const std::vector<lz_hsp>& v, lz_hsp** out, uint64_t* n_out)
+{
+    lz_hsp* res = (lz_hsp*)malloc((v.size() ? v.size() : 1) * sizeof(lz_hsp));
+    if (!res) return lz_fail(LZGPU_ERR_OOM, "host malloc failed");
+    if (!v.empty()) memcpy(res, v.data(), v.size() * sizeof(lz_hsp));
+    *out = res; *n_out = v.size();
+    return 0;
+}
+
+// what both seed-search entry points begin with (args_ok: the caller's test of its pointers)
+static int search_enter(bool args_ok, lz_hsp** out, uint64_t* n_out)
 {
     int rc = require_init(); if (rc) return rc;
-    LzCtx& c = g_ctx;
-    if (!a || !out || !n_out || !a->sub) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    if (!args_ok) return lz_fail(LZGPU_ERR_ARG, "null argument");
     *out = nullptr; *n_out = 0;
-    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "lzgpu_table_prepare has not been called");
+    if (!g_ctx.have_table) return lz_fail(LZGPU_ERR_STATE, "lzgpu_table_prepare has not been called");
+    return 0;
+}
 
-    g_hp.start();
-    // ---- query
-    SeqSlot* qs;
-    if (a->query) {
-        if (a->qlen >= 0x7FFFFFFFu) return LZGPU_NH_SIZE;
-        qs = lz_query_slot(c, -1, true);
-        if ((rc = slot_upload(c, *qs, a->query, a->qlen, false))) return rc;
-    } else {
-        qs = a->query_slot < 0 ? nullptr : lz_query_slot(c, a->query_slot, false);
-        if (!qs) return lz_fail(LZGPU_ERR_ARG, "query slot %d is empty", a->query_slot);
-    }
-    const u8* qhost = a->query ? a->query : qs->host.data();
-    const u32 qlen = qs->len;
-    u32 lo = a->start, hi = a->end ? a->end : qlen;
-    if (hi <= lo) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval is void (%u-%u)", lo, hi);
-    if (hi > qlen) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval end is bad (%u>%u)", hi, qlen);
+struct SeedSearch {                                             // a seed_search in progress: what its steps hand on
+    const lz_search_args* a;
+    SeqSlot* qs = nullptr; const u8* qhost = nullptr;           // the query on the device and on the host
+    u32 lo = 0, hi = 0, n = 0, L = 0;                           // the interval of query positions, its length, the seed's length
+    u64 total_hits = 0;
+    std::vector<LzChunk> chunks; u64 max_chunk = 0;             // [i0,i1) in query positions with at most hit_capacity hits each
+    int mode = 2; bool fused = false;                           // phase-A scan mode; k_scan_hits2 in the place of fill + scan
+    LzExtendParams P; LzLutParams Q;
+    u32 out_cap = 0;
+    std::vector<lz_hsp> plain;                                  // !a->extend: every hit
+};
 
+// ---- 1. the query and the interval of it to search
+static int ss_query(LzCtx& c, SeedSearch& s)
+{
+    const lz_search_args* a = s.a;
+    u32 qlen;
+    int rc = lz_search_query(c, a->query, a->qlen, a->query_slot, true, s.qs, qlen); if (rc) return rc;
+    s.qhost = a->query ? a->query : s.qs->host.data();
+    s.lo = a->start; s.hi = a->end ? a->end : qlen;
+    if (s.hi <= s.lo) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval is void (%u-%u)", s.lo, s.hi);
+    if (s.hi > qlen) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval end is bad (%u>%u)", s.hi, qlen);
+    s.n = s.hi - s.lo; s.L = (u32)c.seed.length;
     g_hp.lap(7, "query slot");
-    // ---- scoring classes, codes
-    // (the class compression and the 4 KiB table upload are skipped when the caller passes the same
-    // matrix as last time -- lastz passes maskedScoring for every strand of every query)
-    static std::vector<s32> last_sub; static u8 rowc[256], colc[256]; static s32 tab[LZ_NCLASS * LZ_NCLASS];
-    u8 cls[256];
-    if (last_sub.size() != 65536 || memcmp(last_sub.data(), a->sub, 65536 * sizeof(s32)) != 0 || !c.score_tab.p) {
-        last_sub.clear();
-        if ((rc = lzh_score_classes(a->sub, rowc, colc, tab))) return rc;
+    return 0;
+}
+
+// ---- 2. scoring classes and the codes of both sequences
+// (the class compression and the 4 KiB table upload are skipped when the caller passes the same
+// matrix as last time -- lastz passes maskedScoring for every strand of every query)
+static int ss_classes(LzCtx& c, SeedSearch& s)
+{
+    const s32* sub = s.a->sub;
+    int rc;
+    if (c.score_sub.size() != 65536 || memcmp(c.score_sub.data(), sub, 65536 * sizeof(s32)) != 0) {
+        s32 tab[LZ_NCLASS * LZ_NCLASS];
+        c.score_sub.clear();
+        if ((rc = lzh_score_classes(sub, c.rowc, c.colc, tab))) return rc;
         if ((rc = c.score_tab.ensure(sizeof(tab)))) return rc;
         LZ_HIP(hipMemcpyAsync(c.score_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c.stream));
         LZ_HIP(hipStreamSynchronize(c.stream));
-        last_sub.assign(a->sub, a->sub + 65536);
+        c.score_sub.assign(sub, sub + 65536);
     }
     g_hp.lap(8, "score classes + table upload");
-    lzh_make_cls(rowc, c.geom.char_to_bits, cls);
-    if ((rc = slot_encode(c, c.target, cls, g_cls_t))) return rc;
-    lzh_make_cls(colc, c.geom.char_to_bits, cls);
-    if ((rc = slot_encode(c, *qs, cls, g_cls_q))) return rc;
-
+    u8 cls[256];
+    lzh_make_cls(c.rowc, c.geom.char_to_bits, cls);
+    if ((rc = slot_encode(c, c.target, cls, c.cls_t))) return rc;
+    lzh_make_cls(c.colc, c.geom.char_to_bits, cls);
+    if ((rc = slot_encode(c, *s.qs, cls, c.cls_q))) return rc;
     g_hp.lap(0, "upload+classes+encode");
-    const u32 L = (u32)c.seed.length;
-    if (qlen < L) return 0;                                     // src/seed_search.c:486-487
+    return 0;
+}
 
-    // ---- state
-    const u32 n = hi - lo;
+// ---- 3. per query position: the raw hits and their exclusive scan; the total and sampled prefix sums on the host
+static const u32 LZ_PLAN_STRIDE = 4096;
+static int ss_count(LzCtx& c, SeedSearch& s)
+{
+    const u32 n = s.n;
+    int rc;
     if ((rc = c.cnt.ensure((size_t)n * 4))) return rc;
     if ((rc = c.off.ensure((size_t)n * 8))) return rc;
     if ((rc = c.pk.ensure((size_t)n * 4))) return rc;
@@ -587,228 +597,174 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     if ((rc = c.dev_counters.ensure(8 * 8))) return rc;
     if ((rc = c.hsp_count.ensure(4))) return rc;
     LZ_HIP(hipMemsetAsync(c.diag_end.p, 0, (size_t)LZ_DIAG_SIZE * 4, c.stream));      // empty_diag_hash
-    LZ_HIP(hipMemsetAsync(c.dev_counters.p, 0, 64, c.stream));
+    LZ_HIP(hipMemsetAsync(c.dev_counters.p, 0, 64, c.stream));                        // [0]=extensions [1]=bp [2]=words
     LZ_HIP(hipMemsetAsync(c.hsp_count.p, 0, 4, c.stream));
-    u64* d_counters = c.dev_counters.as<u64>();                 // [0]=extensions [1]=bp [2]=words
 
-    // ---- 1. count + scan
-    if ((rc = lzk_count_hits(c, qs->code_base(), lo, hi, c.cnt.as<u32>(), c.pk.as<u32>(), c.wiv.as<u32>(), c.wsk.as<u32>(), c.wsv.as<u32>(), d_counters + 2))) return rc;
+    if ((rc = lzk_count_hits(c, s.qs->code_base(), s.lo, s.hi, c.cnt.as<u32>(), c.pk.as<u32>(), c.wiv.as<u32>(), c.wsk.as<u32>(), c.wsv.as<u32>(), c.dev_counters.as<u64>() + 2))) return rc;
     if ((rc = lzk_scan_counts(c, c.cnt.as<u32>(), c.off.as<u64>(), n))) return rc;
 
     // total and the sampled prefix sums for the chunk plan come back through pinned memory the device
     // writes itself: one synchronisation, no staged device-to-host copies
-    const u32 S = 4096;
-    const u32 ns = (n + S - 1) / S;
+    const u32 ns = (n + LZ_PLAN_STRIDE - 1) / LZ_PLAN_STRIDE;
     if (c.pinned_words < (size_t)ns + 16) {
         if (c.pinned) (void)hipHostFree(c.pinned);
         c.pinned = nullptr; c.pinned_words = 0;
         LZ_HIP(hipHostMalloc((void**)&c.pinned, ((size_t)ns + 16) * 8, hipHostMallocDefault));
         c.pinned_words = (size_t)ns + 16;
     }
-    if ((rc = lzk_sample_offsets(c, c.off.as<u64>(), c.cnt.as<u32>(), n, S, ns, c.pinned))) return rc;
+    if ((rc = lzk_sample_offsets(c, c.off.as<u64>(), c.cnt.as<u32>(), n, LZ_PLAN_STRIDE, ns, c.pinned))) return rc;
     c.blk_start_host.assign((size_t)c.blk_count + 1, 0);       // (a chunk's launch of the fill kernel covers its blocks' range of the sorted list)
     LZ_HIP(hipMemcpyAsync(c.blk_start_host.data(), c.blk_start.p, ((size_t)c.blk_count + 1) * 8, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
     g_hp.lap(1, "count+scan (sync)");
     c.timer.resolve();
-    const u64 total_hits = c.pinned[0];
-    const u64* samp = c.pinned + 1;
+    s.total_hits = c.pinned[0];
+    return 0;
+}
 
-    // ---- 2. chunk plan: [i0,i1) in query positions with at most hit_capacity hits each.
-    // Prefix sums are sampled every S positions; finer values are fetched only if a single S-block
-    // exceeds the capacity.
-    std::vector<LzChunk> chunks;
+// ---- 4. chunk plan.  Prefix sums are sampled every LZ_PLAN_STRIDE positions; finer values are fetched only if a
+// single block of that many positions exceeds the capacity.
+static int ss_plan(LzCtx& c, SeedSearch& s)
+{
+    const u64* samp = c.pinned + 1;
     hipError_t fetch_err = hipSuccess;
     auto off_at = [&](u32 i) -> u64 {
-        if (i >= n) return total_hits;
-        if (i % S == 0) return samp[i / S];
+        if (i >= s.n) return s.total_hits;
+        if (i % LZ_PLAN_STRIDE == 0) return samp[i / LZ_PLAN_STRIDE];
         u64 v = 0;
         hipError_t e = hipMemcpy(&v, c.off.as<u64>() + i, 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) fetch_err = e;
         return v;
     };
-    if ((rc = lzh_plan_chunks(n, c.hit_capacity, S, off_at, chunks))) return rc;
+    int rc = lzh_plan_chunks(s.n, c.hit_capacity, LZ_PLAN_STRIDE, off_at, s.chunks); if (rc) return rc;
     if (fetch_err != hipSuccess) return lz_fail(LZGPU_ERR_HIP, "prefix fetch failed: %s", hipGetErrorString(fetch_err));
-
+    for (auto& ch : s.chunks) if (ch.nh > s.max_chunk) s.max_chunk = ch.nh;
     g_hp.lap(2, "chunk plan");
-    LzExtendParams P;
+    return 0;
+}
+
+// ---- 5. the kernels' parameters, the scan mode and its look-up tables.
+// Phase A: four bases per step on 2-bit codes when the matrix, xDrop and the bytes that occur allow it
+// (mode 0 / 1 = without / with special-byte masks), else the byte-code scans (mode 2)
+static int ss_scan_mode(LzCtx& c, SeedSearch& s)
+{
+    const lz_search_args* a = s.a;
+    SeqSlot* qs = s.qs;
+    LzExtendParams& P = s.P; LzLutParams& Q = s.Q;
     P.tcode = c.target.code_base(); P.tlen = c.geom.tlen;
-    P.qcode = qs->code_base();      P.qlen = qlen;
-    P.xdrop = a->xdrop; P.min_score = a->hsp_threshold; P.seed_len = L;
-    P.cls8 = lzh_small_classes(rowc, colc);
+    P.qcode = qs->code_base();      P.qlen = qs->len;
+    P.xdrop = a->xdrop; P.min_score = a->hsp_threshold; P.seed_len = s.L;
+    P.cls8 = lzh_small_classes(c.rowc, c.colc);
     const bool nibs = P.cls8 && c.target.have_nib && qs->have_nib;
     P.tnib = nibs ? c.target.nib.as<u8>() : nullptr; P.qnib = nibs ? qs->nib.as<u8>() : nullptr;
-
-    // phase A: four bases per step on 2-bit codes when the matrix, xDrop and the bytes that occur allow it
-    // (mode 0 / 1 = without / with special-byte masks), else the byte-code scans (mode 2)
-    LzLutParams Q;
     Q.t2 = c.target.two.as<u8>(); Q.q2 = qs->two.as<u8>(); Q.tsp = c.target.spc.as<u8>(); Q.qsp = qs->spc.as<u8>(); Q.xdrop = a->xdrop;
     Q.t2x = c.target.two_x.as<u8>(); Q.tspx = c.target.spc_x.as<u8>();
     Q.tcode = P.tcode; Q.qcode = P.qcode;
-    int mode = 2;
+
+    int mode = 2, rc;
     if (a->extend) {
         s32 M4[16];
         if (lzh_lut_eligible(a->sub, c.geom.char_to_bits, c.target.occ, qs->occ, a->xdrop, M4))
             mode = (c.target.has_special || qs->has_special) ? 1 : 0;
         if (mode < c.min_scan_mode) mode = c.min_scan_mode;         // lzgpu_set_scan_mode (tests): 1 = masks even without specials, 2 = byte-code scans
-        if (mode < 2) {
-            static std::vector<LzLutEntry> lut_host; static s32 lut_m4[16]; static s32 lut_x = -1;
-            if (lut_x != a->xdrop || memcmp(lut_m4, M4, sizeof(M4)) != 0 || !c.lut.p || lut_host.empty()) {
-                lut_host.resize(LZ_LUT_TOTAL);
-                lzh_lut_build(M4, a->xdrop, lut_host.data());
-                if ((rc = c.lut.ensure(lut_host.size() * sizeof(LzLutEntry)))) return rc;
-                memcpy(lut_m4, M4, sizeof(M4)); lut_x = a->xdrop;
-                LZ_HIP(hipMemcpyAsync(c.lut.p, lut_host.data(), lut_host.size() * sizeof(LzLutEntry), hipMemcpyHostToDevice, c.stream));
-                LZ_HIP(hipStreamSynchronize(c.stream));
-            }
+        if (mode < 2 && (c.lut_xdrop != a->xdrop || c.lut_m4.size() != 16 || memcmp(c.lut_m4.data(), M4, sizeof(M4)) != 0)) {
+            std::vector<LzLutEntry> lut_host(LZ_LUT_TOTAL);
+            c.lut_m4.clear();
+            lzh_lut_build(M4, a->xdrop, lut_host.data());
+            if ((rc = c.lut.ensure(lut_host.size() * sizeof(LzLutEntry)))) return rc;
+            LZ_HIP(hipMemcpyAsync(c.lut.p, lut_host.data(), lut_host.size() * sizeof(LzLutEntry), hipMemcpyHostToDevice, c.stream));
+            LZ_HIP(hipStreamSynchronize(c.stream));
+            c.lut_m4.assign(M4, M4 + 16); c.lut_xdrop = a->xdrop;
         }
     }
-    c.last_scan_mode = mode;
-
-    u64 max_chunk = 0;
-    for (auto& ch : chunks) if (ch.nh > max_chunk) max_chunk = ch.nh;
-    // LZGPU_OVERLAP=1: the chunk pipeline over three streams (below); default: one stream, one buffer set
-    static const bool overlap = getenv("LZGPU_OVERLAP") != nullptr && getenv("LZGPU_SERIAL") == nullptr;
-    const int nsets = overlap ? (int)std::min<size_t>(chunks.size() ? chunks.size() : 1, LZ_SETS) : 1;
+    s.mode = c.last_scan_mode = mode;
     // scan mode 0 takes the fused path (k_scan_hits2: enumeration + phase A over the context-inlined table, tagged
-    // records in keys[] and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
+    // records in keys and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
     // the fill variant in use is one the fused kernel does not reproduce (bucket owners), or
     // wctx cannot be had (lz_wctx_prepare)
     static const bool fused_off = getenv("LZGPU_FUSED_SCAN") != nullptr && atoi(getenv("LZGPU_FUSED_SCAN")) == 0;
-    bool fused = a->extend && mode == 0 && max_chunk && !fused_off && c.n_owners <= 1;
-    if (fused && (rc = lz_wctx_prepare(c, fused))) return rc;
+    s.fused = a->extend && mode == 0 && s.max_chunk && !fused_off && c.n_owners <= 1;
+    if (s.fused && (rc = lz_wctx_prepare(c, s.fused))) return rc;
+    return 0;
+}
+
+// ---- 6. the per-chunk buffers, sized once per search for the largest chunk
+static int ss_reserve(LzCtx& c, SeedSearch& s)
+{
+    const bool extend = s.a->extend != 0;
+    const u64 max_chunk = s.max_chunk;
+    int rc;
     if (max_chunk) {
-        if ((rc = c.keys[0].ensure((size_t)max_chunk * 8))) return rc;
-        if (!fused && (rc = c.bins[0].ensure((size_t)max_chunk + 64))) return rc;      // k_fill_hits writes a partition byte per hit on every path (the plain-hit path included)
-        if (a->extend) {
-            const size_t ntiles = (size_t)((max_chunk + LZ_PP_TILE_HOST - 1) / LZ_PP_TILE_HOST), nblocks = (ntiles + 255) / 256;
-            for (int k = 0; k < nsets; k++) {
-                if ((rc = c.keys[k].ensure((size_t)max_chunk * 8))) return rc;
-                if (!fused && (rc = c.bins[k].ensure((size_t)max_chunk + 64))) return rc;
-                if ((rc = c.bin_base[k].ensure(257 * 4))) return rc;
-                if ((rc = c.hist[k].ensure(ntiles * 256 * 4))) return rc;
-                if ((rc = c.hist_part[k].ensure(nblocks * 256 * 4))) return rc;
-                if ((rc = c.run_addr[k].ensure(ntiles * 256 * 4))) return rc;
-            }
-        }
+        if ((rc = c.keys.ensure((size_t)max_chunk * 8))) return rc;
+        if (!s.fused && (rc = c.bins.ensure((size_t)max_chunk + 64))) return rc;       // k_fill_hits writes a partition byte per hit on every path (the plain-hit path included)
     }
-    const u32 out_cap = (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
-    if (a->extend && (rc = c.hsp_out.ensure((size_t)out_cap * sizeof(LzHspRec)))) return rc;
-
-
-    std::vector<lz_hsp> plain;
-    // ---- 3. per chunk, a three-stage pipeline over three streams and two sets of every per-chunk buffer:
-    //   stream  (F): k_fill_hits                              keys                              memory-bound
-    //   stream3 (S): k_scan_hits -> k_scan_tasks              phase A, the 4-byte summaries     VALU-bound
-    //   stream2 (B): k_partition -> k_hist_scan -> k_settle   tiles sorted in place, phase B    latency-bound
-    // so that chunk c's phase B, chunk c+1's scans and chunk c+2's fill share the CUs (the scan kernel leaves
-    // LDS, registers and wave slots for the others' workgroups).  Phase B launches are ordered among themselves
-    // on stream2 (diagEnd carries from chunk to chunk); a buffer set is rewritten only after its last reader.
-    if (a->extend && max_chunk) for (int k = 0; k < nsets; k++) if ((rc = fused ? lzk_fused_reserve(c, k, max_chunk) : lzk_scan_reserve(c, k, mode, max_chunk))) return rc;
-    LZ_HIP(hipEventRecord(c.ev_init, c.stream));              // state resets above are on stream 1
-    LZ_HIP(hipStreamWaitEvent(c.stream2, c.ev_init, 0));
-    LZ_HIP(hipStreamWaitEvent(c.stream3, c.ev_init, 0));
-    size_t ci = 0;
-    // Measured on the bench pair: 219-223 ms per step with the pipeline, 226 ms with everything on one stream --
-    // the scan kernel runs at 75-85 % of the VALU issue rate, ~75 % LDS-pipe occupancy and 3 TB/s of 64-byte
-    // sector fetches at once, so co-resident kernels mostly take turns with it.  The pipeline therefore is opt-in
-    // (LZGPU_OVERLAP=1): by default the stage runs on one stream with one buffer set (5 GiB less to allocate,
-    // per-kernel event times that mean what they say).
-    const bool serial = !overlap;
-    hipStream_t sF = c.stream, sS = serial ? c.stream : c.stream3, sB = serial ? c.stream : c.stream2;
-    // phase B needs whole CUs (128 VGPRs x 1024 lanes) and cannot share one with the scan kernel: it runs on the
-    // scans' stream, behind the NEXT chunk's scans, by which time its partition (which does overlap them) is done
-    u64 set_n[LZ_SETS] = {};                                    // hits of the chunk a set holds
-    auto settle = [&](int set) -> int {
-        LZ_HIP(hipStreamWaitEvent(sS, c.ev_part[set], 0));
-        int r = lzk_settle(c, P, c.keys[set].as<u64>(), set_n[set], c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.run_addr[set].as<u32>(), c.bin_base[set].as<u32>(), c.diag_end.as<u32>(), c.score_tab.as<s32>(),
-                           c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap, d_counters, sS);
-        if (r) return r;
-        LZ_HIP(hipEventRecord(c.ev_extended[set], sS));
-        return 0;
-    };
-    int pending = -1;                                           // set whose phase B is still to be launched
-    for (auto& ch : chunks) {
-        const int set = (int)(ci % (size_t)nsets);
-        if (!a->extend) {                                       // process_for_plain_hit: report every hit
-            if ((rc = lzk_fill_hits(c, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, c.keys[0].as<u64>(), sF))) return rc;
-            std::vector<u64> hk(ch.nh);
-            LZ_HIP(hipMemcpyAsync(hk.data(), c.keys[0].p, (size_t)ch.nh * 8, hipMemcpyDeviceToHost, c.stream));
-            LZ_HIP(hipStreamSynchronize(c.stream));
-            for (u64 k : hk) { u32 p2 = (u32)k; plain.push_back({ p2 + (u32)(k >> 32), p2, L, 0 }); }
-            continue;
-        }
-        const bool reuse = ci >= (size_t)nsets;                 // the set has been through the pipeline before
-        if (reuse && pending == set) { if ((rc = settle(pending))) return rc; pending = -1; }   // (fewer than three sets)
-        // F: keys (every buffer of the set is free once its phase B is done)
-        if (reuse) LZ_HIP(hipStreamWaitEvent(sF, c.ev_extended[set], 0));
-        if (fused) {
-            // the fused launch in the place of fill + scans (on the scans' stream, behind the set's last reader), then
-            // the tagged records sorted tile by tile where they lie, and the runs' ranks from the counts that leaves
-            LZ_HIP(hipEventRecord(c.ev_keys[set], sF));
-            LZ_HIP(hipStreamWaitEvent(sS, c.ev_keys[set], 0));
-            if ((rc = lzk_scan_fused(c, set, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, ch.nh, P, Q,
-                                     c.lut.as<LzLutEntry>(), c.keys[set].as<u64>(), sS))) return rc;
-            LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
-            LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-            if ((rc = lzk_partition(c, true, c.keys[set].as<u64>(), nullptr, ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
-            if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
-            set_n[set] = ch.nh;
-            LZ_HIP(hipEventRecord(c.ev_part[set], sB));
-            if (pending >= 0) { if ((rc = settle(pending))) return rc; }
-            pending = set;
-            ci++;
-            continue;
-        }
-        if ((rc = lzk_fill_hits(c, lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), n, c.off.as<u64>(), ch.base, c.keys[set].as<u64>(), sF))) return rc;
-        LZ_HIP(hipEventRecord(c.ev_keys[set], sF));
-        // S: the scans
-        LZ_HIP(hipStreamWaitEvent(sS, c.ev_keys[set], 0));
-        if ((rc = lzk_scan_hits(c, set, mode, P, Q, c.keys[set].as<u64>(), ch.nh, c.score_tab.as<s32>(), c.lut.as<LzLutEntry>(), c.bins[set].as<u8>(), sS))) return rc;
-        LZ_HIP(hipEventRecord(c.ev_summ[set], sS));
-        // B: the partition
-        LZ_HIP(hipStreamWaitEvent(sB, c.ev_summ[set], 0));
-        if ((rc = lzk_partition(c, false, c.keys[set].as<u64>(), c.summ[set].as<u32>(), ch.nh, c.hist[set].as<u32>(), c.run_addr[set].as<u32>(), sB))) return rc;
-        if ((rc = lzk_hist_scan(c, ch.nh, c.hist[set].as<u32>(), c.hist_part[set].as<u32>(), c.bin_base[set].as<u32>(), sB))) return rc;
-        set_n[set] = ch.nh;
-        LZ_HIP(hipEventRecord(c.ev_part[set], sB));
-        // S again: phase B of the previous chunk (diagEnd carries from chunk to chunk: chunk order)
-        if (pending >= 0) { if ((rc = settle(pending))) return rc; }
-        pending = set;
-        ci++;
+    if (extend && max_chunk) {
+        const size_t ntiles = (size_t)((max_chunk + LZ_PP_TILE_HOST - 1) / LZ_PP_TILE_HOST), nblocks = (ntiles + 255) / 256;
+        if ((rc = c.bin_base.ensure(257 * 4))) return rc;
+        if ((rc = c.hist.ensure(ntiles * 256 * 4))) return rc;
+        if ((rc = c.hist_part.ensure(nblocks * 256 * 4))) return rc;
+        if ((rc = c.run_addr.ensure(ntiles * 256 * 4))) return rc;
     }
-    if (pending >= 0) { if ((rc = settle(pending))) return rc; }
-    g_hp.lap(3, "chunk loop launches");
-    LZ_HIP(hipStreamSynchronize(c.stream3));
-    LZ_HIP(hipStreamSynchronize(c.stream2));
-    g_hp.lap(4, "wait for GPU");
+    s.out_cap = (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
+    if (extend && (rc = c.hsp_out.ensure((size_t)s.out_cap * sizeof(LzHspRec)))) return rc;
+    if (extend && max_chunk && (rc = s.fused ? lzk_fused_reserve(c, max_chunk) : lzk_scan_reserve(c, s.mode, max_chunk))) return rc;
+    return 0;
+}
 
+// ---- 7. one chunk: enumeration + phase A (one launch or two), the records sorted tile by tile where they lie, the runs'
+// ranks from the counts that leaves, phase B.  All on c.stream: diagEnd carries from chunk to chunk, in chunk order.
+static int ss_chunk(LzCtx& c, SeedSearch& s, const LzChunk& ch)
+{
+    const LzExtendParams& P = s.P;
+    u64* keys = c.keys.as<u64>();
+    hipStream_t st = c.stream;
+    int rc;
+    if (s.fused) {
+        if ((rc = lzk_scan_fused(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, ch.nh, P, s.Q, c.lut.as<LzLutEntry>(), keys, st))) return rc;
+    } else {
+        if ((rc = lzk_fill_hits(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, keys, st))) return rc;
+        if ((rc = lzk_scan_hits(c, s.mode, P, s.Q, keys, ch.nh, c.score_tab.as<s32>(), c.lut.as<LzLutEntry>(), c.bins.as<u8>(), st))) return rc;
+    }
+    if ((rc = lzk_partition(c, s.fused, keys, s.fused ? nullptr : c.summ.as<u32>(), ch.nh, c.hist.as<u32>(), c.run_addr.as<u32>(), st))) return rc;
+    if ((rc = lzk_hist_scan(c, ch.nh, c.hist.as<u32>(), c.hist_part.as<u32>(), c.bin_base.as<u32>(), st))) return rc;
+    return lzk_settle(c, P, keys, ch.nh, c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(), c.diag_end.as<u32>(), c.score_tab.as<s32>(),
+                      c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), s.out_cap, c.dev_counters.as<u64>(), st);
+}
+// ... of a search without extension (process_for_plain_hit): every hit is reported
+static int ss_chunk_plain(LzCtx& c, SeedSearch& s, const LzChunk& ch)
+{
+    int rc = lzk_fill_hits(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, c.keys.as<u64>(), c.stream); if (rc) return rc;
+    std::vector<u64> hk(ch.nh);
+    LZ_HIP(hipMemcpyAsync(hk.data(), c.keys.p, (size_t)ch.nh * 8, hipMemcpyDeviceToHost, c.stream));
+    LZ_HIP(hipStreamSynchronize(c.stream));
+    for (u64 k : hk) { u32 p2 = (u32)k; s.plain.push_back({ p2 + (u32)(k >> 32), p2, s.L, 0 }); }
+    return 0;
+}
+
+// ---- 8. counters; the candidates' match counts; host finish: discovery order, entropy, threshold
+static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
+{
+    const lz_search_args* a = s.a;
+    int rc;
     u64 hc[3] = { 0, 0, 0 }; u32 n_rec = 0;
-    LZ_HIP(hipMemcpyAsync(hc, d_counters, 24, hipMemcpyDeviceToHost, c.stream));
+    LZ_HIP(hipMemcpyAsync(hc, c.dev_counters.p, 24, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipMemcpyAsync(&n_rec, c.hsp_count.p, 4, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
-    const bool gpu_counts = a->extend && n_rec > 0 && n_rec <= (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
+    g_hp.lap(4, "wait for GPU");
+    const bool gpu_counts = a->extend && n_rec > 0 && n_rec <= s.out_cap;
     if (gpu_counts) {
         if ((rc = c.hsp_mc.ensure((size_t)n_rec * 20))) return rc;
         if ((rc = lzk_hsp_match_counts(c, c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), n_rec, n_rec,
-                                       c.target.raw_base(), qs->raw_base(), c.target.code_base(), qs->code_base(),
+                                       c.target.raw_base(), s.qs->raw_base(), c.target.code_base(), s.qs->code_base(),
                                        c.hsp_mc.as<u32>(), c.stream))) return rc;
     }
     c.timer.resolve();
     { std::lock_guard<std::mutex> lk(c.counters_m);
-      c.counters.words += hc[2]; c.counters.raw_hits += total_hits;
+      c.counters.words += hc[2]; c.counters.raw_hits += s.total_hits;
       c.counters.extensions += hc[0]; c.counters.bp_extended += hc[1]; }
+    if (!a->extend) return lz_hsps_out(s.plain, out, n_out);
+    if (n_rec > s.out_cap) return LZGPU_NH_HSP_OVERFLOW;
 
-    if (!a->extend) {
-        lz_hsp* res = (lz_hsp*)malloc((plain.size() ? plain.size() : 1) * sizeof(lz_hsp));
-        if (!res) return lz_fail(LZGPU_ERR_OOM, "host malloc failed");
-        if (!plain.empty()) memcpy(res, plain.data(), plain.size() * sizeof(lz_hsp));
-        *out = res; *n_out = plain.size();
-        return 0;
-    }
-    if (n_rec > out_cap) return LZGPU_NH_HSP_OVERFLOW;
-
-    // ---- 4. host finish: discovery order, entropy, threshold
     std::vector<LzHspRec> recs(n_rec);
     std::vector<u32> mc;
     if (n_rec) LZ_HIP(hipMemcpyAsync(recs.data(), c.hsp_out.p, (size_t)n_rec * sizeof(LzHspRec), hipMemcpyDeviceToHost, c.stream));
@@ -817,21 +773,39 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     c.timer.resolve();
     g_hp.lap(5, "copy candidates");
     std::vector<lz_hsp> fin;
-    if ((rc = lzh_finish_hsps(recs.data(), n_rec, c.target.host.data(), qhost, c.seed, c.geom.char_to_bits,
+    if ((rc = lzh_finish_hsps(recs.data(), n_rec, c.target.host.data(), s.qhost, c.seed, c.geom.char_to_bits,
                               a->hsp_threshold, a->entropic, fin, gpu_counts ? mc.data() : nullptr, &c.last_order)))
         return lz_fail(rc, "internal: candidate HSP is not on a seed hit");
-    lz_hsp* res = (lz_hsp*)malloc((fin.size() ? fin.size() : 1) * sizeof(lz_hsp));
-    if (!res) return lz_fail(LZGPU_ERR_OOM, "host malloc failed");
-    if (!fin.empty()) memcpy(res, fin.data(), fin.size() * sizeof(lz_hsp));
+    if ((rc = lz_hsps_out(fin, out, n_out))) return rc;
     { std::lock_guard<std::mutex> lk(c.counters_m); c.counters.hsps += fin.size(); }
     g_hp.lap(6, "host finish (order+entropy)");
-    *out = res; *n_out = fin.size();
     return 0;
+}
+
+// the search proper (after search_enter); with c.self.mode != LZ_SELF_OFF the count, fill and fused scan kernels drop
+// the hits a self-comparison drops
+static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
+{
+    LzCtx& c = g_ctx;
+    SeedSearch s; s.a = a;
+    int rc;
+    g_hp.start();
+    if ((rc = ss_query(c, s))) return rc;
+    if ((rc = ss_classes(c, s))) return rc;
+    if (s.qs->len < s.L) return 0;                              // src/seed_search.c:486-487
+    if ((rc = ss_count(c, s))) return rc;
+    if ((rc = ss_plan(c, s))) return rc;
+    if ((rc = ss_scan_mode(c, s))) return rc;
+    if ((rc = ss_reserve(c, s))) return rc;
+    for (const LzChunk& ch : s.chunks) if ((rc = a->extend ? ss_chunk(c, s, ch) : ss_chunk_plain(c, s, ch))) return rc;
+    g_hp.lap(3, "chunk loop launches");
+    return ss_finish(c, s, out, n_out);
 }
 
 extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
 {
-    return seed_search(a, out, n_out);
+    int rc = search_enter(a && out && n_out && a->sub, out, n_out);
+    return rc ? rc : seed_search(a, out, n_out);
 }
 
 // Self-comparison (lastz --self, --band).  Every raw hit the reference drops (src/seed_search.c:841-848, 903-908,
@@ -840,17 +814,10 @@ extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint
 // interval, and everything after them runs unchanged on the surviving hits.
 extern "C" int lzgpu_seed_hit_search_self(const lz_search_args* a, const lz_self_args* s, lz_hsp** out, uint64_t* n_out)
 {
-    int rc = require_init(); if (rc) return rc;
+    int rc = search_enter(a && s && out && n_out && a->sub, out, n_out); if (rc) return rc;
     LzCtx& c = g_ctx;
-    if (!a || !s || !out || !n_out || !a->sub) return lz_fail(LZGPU_ERR_ARG, "null argument");
-    *out = nullptr; *n_out = 0;
-    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "lzgpu_table_prepare has not been called");
-    u32 qlen = a->qlen;
-    if (!a->query) {
-        const SeqSlot* qs = a->query_slot < 0 ? nullptr : lz_query_slot(c, a->query_slot, false);
-        if (!qs) return lz_fail(LZGPU_ERR_ARG, "query slot %d is empty", a->query_slot);
-        qlen = qs->len;
-    }
+    SeqSlot* qs; u32 qlen;                                      // (the length only: seed_search uploads a host-pointer query)
+    if ((rc = lz_search_query(c, a->query, a->qlen, a->query_slot, false, qs, qlen))) return rc;
     // what the kernels assume (seed_hit_below_diagonal's note (1), :2068-2070): one sequence against itself
     if (qlen != c.geom.tlen) return LZGPU_NH_UNSUPPORTED;
     if (s->band_width != 0 && !s->same_strand) return LZGPU_NH_UNSUPPORTED;      // (the reference bands the same strand only, :844)
@@ -896,15 +863,8 @@ extern "C" int lzgpu_window_search(const lz_window_search_args* a, lz_hsp** out,
     LzSeedDev sd;
     if ((rc = lzh_seed_to_dev(a->seed, sd))) return rc;
     if (sd.nprobes != 1 || sd.weight > 14) return LZGPU_NH_UNSUPPORTED;
-    SeqSlot* qs;
-    if (a->query) {
-        if (a->qlen >= 0x7FFFFFFFu) return LZGPU_NH_SIZE;
-        qs = lz_query_slot(c, -1, true);
-        if ((rc = slot_upload(c, *qs, a->query, a->qlen, false))) return rc;
-    } else {
-        qs = a->query_slot < 0 ? nullptr : lz_query_slot(c, a->query_slot, false);
-        if (!qs) return lz_fail(LZGPU_ERR_ARG, "query slot %d is empty", a->query_slot);
-    }
+    SeqSlot* qs; u32 qlen;
+    if ((rc = lz_search_query(c, a->query, a->qlen, a->query_slot, true, qs, qlen))) return rc;
     for (u32 k = 0; k < a->n_windows; k++) {
         const lz_window& w = a->windows[k];
         if (w.t_len > 20480 || w.q_len > 20480) return LZGPU_NH_UNSUPPORTED;
@@ -918,9 +878,9 @@ extern "C" int lzgpu_window_search(const lz_window_search_args* a, lz_hsp** out,
     LZ_HIP(hipMemcpyAsync(wtab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
     lzh_make_cls(rowc, a->char_to_bits, cls);
-    if ((rc = slot_encode(c, c.target, cls, g_cls_t))) return rc;
+    if ((rc = slot_encode(c, c.target, cls, c.cls_t))) return rc;
     lzh_make_cls(colc, a->char_to_bits, cls);
-    if ((rc = slot_encode(c, *qs, cls, g_cls_q))) return rc;
+    if ((rc = slot_encode(c, *qs, cls, c.cls_q))) return rc;
     LzExtendParams P; memset(&P, 0, sizeof(P));
     P.tcode = c.target.code_base(); P.tlen = c.target.len; P.qcode = qs->code_base(); P.qlen = qs->len;
     P.xdrop = a->xdrop; P.min_score = a->hsp_threshold; P.seed_len = (u32)sd.length;

@@ -1117,49 +1117,49 @@ static int lz_scan_tpb(int mode)
     if (mode != 0) return LZ_SC_TPB;
     return (env == 512 || env == 640 || env == 768 || env == 1024) ? env : 640;     // 640: five waves per SIMD at 89 VGPRs (512: 72.5, 640: 69.7, 768 with 8 spilled registers: 75.9 ms per step)
 }
-// The task list of a set for n hits scanned by n_regions waves (k_scan_hits in `mode`, or k_scan_hits2 as mode 0): one region
+// The task list for n hits scanned by n_regions waves (k_scan_hits in `mode`, or k_scan_hits2 as mode 0): one region
 // per wave, room for 1/32 of the wave's hits + 64; a hit that finds its region full is left to phase B.
 // (64 B each; ~3 % of the hits become tasks on plain sequences: 1/32 of them fit, 2 GiB less to allocate than with 1/8.
 // With special bytes that do not end a scan -- IUPAC codes -- every window that meets one goes on as a task as well:
 // 1/12, or the overflow lands on phase B's slow path: 1 % of the hits there took k_settle2 from 20 to 84 ms.)
-static int lz_task_regions(LzCtx& c, int set, int mode, u64 n, u32 n_regions, u32& region_cap)
+static int lz_task_regions(LzCtx& c, int mode, u64 n, u32 n_regions, u32& region_cap)
 {
     region_cap = (u32)std::min<u64>(n / (mode == 1 ? 12 : 32) / n_regions + 64, 1u << 20);
     static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook: tiny regions, so that hits find theirs full
     if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
     int rc;
-    if (mode < 2 && (rc = c.scan_tasks[set].ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
-    return c.scan_ntasks[set].ensure((size_t)n_regions * 4);
+    if (mode < 2 && (rc = c.scan_tasks.ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
+    return c.scan_ntasks.ensure((size_t)n_regions * 4);
 }
-// grid of k_scan_hits for n hits, and the set's summaries and task list
-static int lz_scan_buffers(LzCtx& c, int set, int mode, u64 n, u32& grid, u32& n_regions, u32& region_cap)
+// grid of k_scan_hits for n hits, and the summaries and task list
+static int lz_scan_buffers(LzCtx& c, int mode, u64 n, u32& grid, u32& n_regions, u32& region_cap)
 {
     const u32 wpg = (u32)lz_scan_tpb(mode) / 64u;
-    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
+    const int cus = c.num_cus;
     static const u32 wgs = getenv("LZGPU_PP_WGS") ? (u32)atoi(getenv("LZGPU_PP_WGS")) : 2u;
     const u64 nspans = (n + 64u * LZ_SC_ROUNDS - 1) / (64u * LZ_SC_ROUNDS), want = (nspans + wpg - 1) / wpg;
     grid = (u32)std::min<u64>(want ? want : 1, (u64)wgs * (u64)cus);
     n_regions = grid * wpg;
-    const int rc = c.summ[set].ensure((size_t)n * 4);
-    return rc ? rc : lz_task_regions(c, set, mode, n, n_regions, region_cap);
+    const int rc = c.summ.ensure((size_t)n * 4);
+    return rc ? rc : lz_task_regions(c, mode, n, n_regions, region_cap);
 }
-// buffers of a set for chunks of up to max_n hits (sized once per search: chunk sizes differ a little, and a
+// those buffers for chunks of up to max_n hits (sized once per search: chunk sizes differ a little, and a
 // device buffer that grows is freed and allocated again)
-int lzk_scan_reserve(LzCtx& c, int set, int mode, u64 max_n)
+int lzk_scan_reserve(LzCtx& c, int mode, u64 max_n)
 {
     u32 grid, n_regions, region_cap;
-    return lz_scan_buffers(c, set, mode, max_n, grid, n_regions, region_cap);
+    return lz_scan_buffers(c, mode, max_n, grid, n_regions, region_cap);
 }
 
-int lzk_scan_hits(LzCtx& c, int set, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
+int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
                   const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st)
 {
     if (n == 0) return 0;
-    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
+    const int cus = c.num_cus;
     int rc;
     u32 grid, n_regions, task_cap;
-    if ((rc = lz_scan_buffers(c, set, mode, n, grid, n_regions, task_cap))) return rc;
-    u32* summ = c.summ[set].as<u32>(); LzScanTask* tasks = c.scan_tasks[set].as<LzScanTask>(); u32* ntk = c.scan_ntasks[set].as<u32>();
+    if ((rc = lz_scan_buffers(c, mode, n, grid, n_regions, task_cap))) return rc;
+    u32* summ = c.summ.as<u32>(); LzScanTask* tasks = c.scan_tasks.as<LzScanTask>(); u32* ntk = c.scan_ntasks.as<u32>();
     c.timer.begin("k_scan_hits", st);
     const int tpb = lz_scan_tpb(mode);
 #define LZ_SCAN_LAUNCH(M_, T_, W_) hipLaunchKernelGGL((k_scan_hits<M_, T_, W_>), dim3(grid), dim3(T_), 0, st, P, Q, keys, n, score_tab, lut, summ, bins, tasks, ntk, task_cap)
@@ -1383,20 +1383,20 @@ static u32 lz_fused_tpb(LzCtx& c)
     if (c.self.mode != LZ_SELF_OFF) return 512u;
     return (env == 512 || env == 768 || env == 1024) ? (u32)env : 1024u;
 }
-// the fused kernel's grid (one workgroup per CU: its LDS) and the set's task list
-static int lz_fused_buffers(LzCtx& c, int set, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
+// the fused kernel's grid (one workgroup per CU: its LDS) and the task list
+static int lz_fused_buffers(LzCtx& c, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
 {
-    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
+    const int cus = c.num_cus;
     grid = (u32)cus; n_regions = grid * (lz_fused_tpb(c) / 64u);
-    return lz_task_regions(c, set, 0, n_hits, n_regions, region_cap);
+    return lz_task_regions(c, 0, n_hits, n_regions, region_cap);
 }
-int lzk_fused_reserve(LzCtx& c, int set, u64 max_n)
+int lzk_fused_reserve(LzCtx& c, u64 max_n)
 {
     u32 grid, n_regions, region_cap;
-    return lz_fused_buffers(c, set, max_n, grid, n_regions, region_cap);
+    return lz_fused_buffers(c, max_n, grid, n_regions, region_cap);
 }
 // lzk_fill_hits + lzk_scan_hits of mode 0 in one launch: the chunk's hits as tagged records, in discovery order
-int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
+int lzk_scan_fused(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
                    const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st)
 {
     if (n == 0 || i1 <= i0 || n_hits == 0) return 0;
@@ -1404,8 +1404,8 @@ int lzk_scan_fused(LzCtx& c, int set, u32 lo, u32 i0, u32 i1, const u32* sk, con
     if (n == 0) return 0;
     int rc;
     u32 grid, n_regions, region_cap;
-    if ((rc = lz_fused_buffers(c, set, n_hits, grid, n_regions, region_cap))) return rc;
-    LzScanTask* tasks = c.scan_tasks[set].as<LzScanTask>(); u32* ntk = c.scan_ntasks[set].as<u32>();
+    if ((rc = lz_fused_buffers(c, n_hits, grid, n_regions, region_cap))) return rc;
+    LzScanTask* tasks = c.scan_tasks.as<LzScanTask>(); u32* ntk = c.scan_ntasks.as<u32>();
     c.timer.begin("k_scan_hits", st);
     const u32 tpb = lz_fused_tpb(c);
 #define LZ_FUSED_LAUNCH(S_, T_, C_, self_) hipLaunchKernelGGL((k_scan_hits2<S_, T_, C_>), dim3(grid), dim3(T_), 0, st, lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), \

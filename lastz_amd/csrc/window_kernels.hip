@@ -195,7 +195,7 @@ int lzk_window_search(LzCtx& c, const LzExtendParams& P, const LzSeedDev& sd, co
     out.clear(); counts.assign(n, 0);
     if (n == 0) return 0;
     int rc;
-    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device);
+    const int cus = c.num_cus;
     const u32 grid = std::min<u32>(n, (u32)cus);
     std::vector<LzWinJob> jobs(n);
     for (u32 k = 0; k < n; k++) { jobs[k].t_off = wins[k].t_off; jobs[k].t_len = wins[k].t_len; jobs[k].q_off = wins[k].q_off; jobs[k].q_len = wins[k].q_len; }

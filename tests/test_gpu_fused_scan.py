@@ -34,7 +34,7 @@ def runs(gpu, tmp_path_factory):
     out = {}
     for key, cases, fused, extra in RUNS:
         env = dict(os.environ); env.update(extra); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_OVERLAP", "LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY"):
+        for k in ("LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY"):
             env.pop(k, None)
         fn = str(d / (key + ".npz"))
         r = subprocess.run([sys.executable, CHILD, fn] + cases, capture_output=True, text=True, timeout=600, env=env)

@@ -297,9 +297,10 @@ def test_two_mbp_pair_and_capacity_invariance(gpu):
         assert (a == b).all()
 
 
-def test_three_stream_chunk_pipeline(gpu, tmp_path):
-    """LZGPU_OVERLAP=1 (fill + histogram | scans | partition, phase B behind the next chunk's scans, three buffer
-    sets) gives the same HSP list as the one-stream default: many small chunks, both strands, fresh process."""
+def test_many_small_chunks_in_a_fresh_process(gpu, tmp_path):
+    """many small chunks (hit capacities 150,000 and 700,000: about 21 and 5 per strand, about nine tiles per small one),
+    both strands, in a fresh process: diagEnd carries from chunk to chunk, and the HSP list is the one-chunk list of
+    this process.  Once on the fused scan path (LZGPU_FUSED_SCAN unset) and once on the split one (=0)."""
     t, q = seqio.synth_pair(2_000_000, 2_000_000, seed=12)
     _, masked = H.scoring()
     _prep(gpu, t)
@@ -315,10 +316,47 @@ def test_three_stream_chunk_pipeline(gpu, tmp_path):
             "    for k, (_, _, qq) in enumerate(H.strands(q)):\n"
             "        got = g.seed_hit_search(masked, q=qq); want = np.load(%r %% k)\n"
             "        assert len(got) == len(want) and (got == want).all(), (cap, k)\n"
-            "print('pipeline ok')\n" % (H.ROOT, os.path.join(H.ROOT, "tests"), str(tmp_path / "want%d.npy")))
-    env = dict(os.environ); env["LZGPU_OVERLAP"] = "1"; env.pop("LZGPU_SERIAL", None)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "pipeline ok" in r.stdout, r.stdout + r.stderr
+            "print('chunks ok')\n" % (H.ROOT, os.path.join(H.ROOT, "tests"), str(tmp_path / "want%d.npy")))
+    for fused in (None, "0"):
+        env = dict(os.environ); env.pop("LZGPU_FUSED_SCAN", None)
+        if fused is not None:
+            env["LZGPU_FUSED_SCAN"] = fused
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0 and "chunks ok" in r.stdout, (fused, r.stdout + r.stderr)
+
+
+def test_same_results_after_shutdown_and_init(gpu):
+    """a search in several chunks (blk_start holds several blocks of positions) and an opposite-strand self search of a
+    [multi] sequence (self_sep holds its separators), then shutdown + init: the same two searches give the same HSPs
+    and counters as before.  A guard on results: that shutdown releases every buffer is read off
+    LzCtx::release_device_memory (lz_ctx.hpp), not shown here -- on one device a stale pointer would still work."""
+    import self_cases as S
+    _, masked = H.scoring()
+    t, q = seqio.synth_pair(300_000, 120_000, seed=77)
+    c = S.CASES["multi_ragged"]
+    v, seps, _ = S.sequence("multi_ragged")
+
+    def searches():
+        try:
+            gpu.set_hit_capacity(4096)                      # ~28,000 expected hits: 16 blocks, several chunks
+            tab = _prep(gpu, t)
+            a = _same_hsps(gpu, tab, q, masked)
+            ca = gpu.counters()
+        finally:
+            gpu.set_hit_capacity(1 << 28)
+        gpu.table_prepare(v, gpu.seed(c["pattern"], c["trans"]), CTB, step=c["step"])
+        gpu.counters_reset()
+        b = gpu.seed_hit_search_self(masked, q=S.minus(v, seps), same_strand=False, sep1=seps, sep2=seps)
+        return a, ca, b, gpu.counters()
+
+    a0, ca0, b0, cb0 = searches()
+    want, _ = lzo.seed_hit_search(lzo.Table(v, lzo.seed(c["pattern"], c["trans"]), step=c["step"]), S.minus(v, seps), masked,
+                                  self_strand="opposite", sep1=seps, sep2=seps)
+    assert len(a0) > 0 and len(b0) == len(want) > 0 and (b0 == want).all()
+    gpu.shutdown(); gpu.init()
+    a1, ca1, b1, cb1 = searches()
+    assert len(a1) == len(a0) and (a1 == a0).all() and ca1 == ca0
+    assert len(b1) == len(b0) and (b1 == b0).all() and cb1 == cb0
 
 
 def test_full_task_regions_leave_hits_to_phase_b(gpu, tmp_path):

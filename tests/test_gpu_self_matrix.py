@@ -46,7 +46,7 @@ def runs(gpu, tmp_path_factory):
     out = {}
     for key, cases, fused in RUNS:
         env = dict(os.environ); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_OVERLAP", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
+        for k in ("LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
             env.pop(k, None)
         fn = str(d / (key + ".npz"))
         t0 = time.perf_counter()

@@ -43,7 +43,7 @@ def runs(gpu, tmp_path_factory):
     out = {}
     for key, cases, mode, fused in RUNS:
         env = dict(os.environ); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_OVERLAP", "LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
+        for k in ("LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
             env.pop(k, None)
         fn = str(d / (key + ".npz"))
         r = subprocess.run([sys.executable, CHILD, fn, str(mode)] + cases, capture_output=True, text=True, timeout=300, env=env)
