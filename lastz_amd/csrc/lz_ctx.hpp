@@ -111,6 +111,19 @@ struct LzCtx {
     DevBuf hsp_mc;                  // [n][5]: A/C/G/T match counts of the candidates (entropy inputs) + probe index
     DevBuf dev_counters;            // u64[8]
     DevBuf tb_keys, tb_vals, tb_keys2, tb_vals2;   // table build scratch
+    // ---- gapped stage (B3) and window search: device memory and settings that used to live at file scope
+    // Threading: `dp` is touched on dp_stream only, by lzgpu_gapped_extend_batch's caller before its workers start and then by whichever
+    // worker holds the batch rendezvous (HipDpExec::run_multi: one at a time); the win_* buffers on `stream` only, by lzgpu_window_search's caller.
+    struct DpBufs { DevBuf jobs, ids, res, tab, tb, rows, ops, ops_off, ops_out, pieces, rings, sel_jobs, sel_res, problems; } dp;
+    DevBuf win_jobs, win_scratch, win_out, win_count;
+    bool win_attr_set = false;        // k_window_search's dynamic-LDS attribute has been set on this device context (lzgpu_shutdown clears it)
+    u64 dp_longest[4] = { 0, 0, 0, 0 };   // lzgpu_dp_longest: rows, cells, sweep and traceback ticks of the DP that swept the most rows since the last reset
+    // the two settings below keep their value across shutdown + init, as hit_capacity does
+    u32 dp_slot_tb = 8u << 20;        // lzgpu_set_dp_slot: the uniform traceback slot (bytes) per DP
+    // Anchors speculated per round.  A launch lasts as long as its longest DP, so the fewer rounds the better: 2048 holds
+    // the ~1150 anchors of a 50 Mbp strand that need a DP in one launch; a 200 Mbp strand has ~4500 (north star:
+    // 7 launches, 0.73 s at 2048; 5 launches, 0.48 s at 8192 and beyond).  Default: 1/32 of the anchors, within [2048, 16384].
+    u32 dp_window = 0;                // 0: the default rule; lzgpu_set_dp_window / LZGPU_DP_WINDOW fix it
     u32 n_owners = 1, owner = 0;      // bucket ownership (lzgpu_set_bucket_owner)
     LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self); mode LZ_SELF_OFF otherwise
     DevBuf self_sep;                  // its separators on the device: sep1, then sep2
@@ -131,7 +144,9 @@ struct LzCtx {
     {
         DevBuf* all[] = { &wstart, &wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
                           &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab,
-                          &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep };
+                          &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep,
+                          &dp.jobs, &dp.ids, &dp.res, &dp.tab, &dp.tb, &dp.rows, &dp.ops, &dp.ops_off, &dp.ops_out, &dp.pieces, &dp.rings, &dp.sel_jobs, &dp.sel_res, &dp.problems,
+                          &win_jobs, &win_scratch, &win_out, &win_count };
         for (DevBuf* b : all) b->release();
         target.release();
         for (auto& kv : queries) kv.second.release();
@@ -140,6 +155,7 @@ struct LzCtx {
         pinned = nullptr; pinned_words = 0;
         have_table = false; wctx_gen = 0; wctx_code_key = 0;
         score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
+        win_attr_set = false;
     }
 };
 

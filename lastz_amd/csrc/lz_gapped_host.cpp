@@ -394,39 +394,482 @@ static bool partition_limits(const u32* sep, u32 n_sep, u32 pos, u32 len, u32& l
     return true;
 }
 
+static inline u8 fold_case(u8 x) { return (x >= 'a' && x <= 'z') ? (u8)(x - 32) : x; }      // dna_toupper
+
 static bool same_bases(const u8* a, const u8* b, u32 n)
 {
-    for (u32 i = 0; i < n; i++) {
-        u8 x = a[i], y = b[i];
-        if (x >= 'a' && x <= 'z') x -= 32;
-        if (y >= 'a' && y <= 'z') y -= 32;
-        if (x != y) return false;
-    }
+    for (u32 i = 0; i < n; i++) if (fold_case(a[i]) != fold_case(b[i])) return false;
     return true;
 }
 
-int lzh_gapped_extend(const LzGappedParams& G, LzDpExecutor& exec, lz_segment* anchors, u32 n_anchors,
-                      std::vector<lz_align>& out, std::vector<u32>& out_ops, LzGappedStats& st)
+// ---------------------------------------------------------------------------------------------------------------
+// lzh_gapped_extend: the anchor pass.  Its steps are the member functions of GappedPass, in the order they run.
+
+namespace {                                                     // (everything up to lzh_gapped_extend is private to this file)
+
+// LZGPU_HOSTPROF=1: where the host time of the stage goes.  The phases of a round follow each other and are lapped
+// (lap); the parts of the commit pass are timed by scope (Scope).  Neither reads a clock while profiling is off.
+struct GappedProf {
+    const bool on;
+    double sort = 0, window = 0, exec = 0, prebuild = 0, commit = 0;                  // the phases
+    double c_lr = 0, c_chk = 0, c_build = 0, c_ins = 0, c_alr = 0, c_cov = 0;         // inside commit (c_build holds c_ins and c_cov, c_ins holds c_alr)
+    double mark;
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    static bool enabled() { static const bool e = getenv("LZGPU_HOSTPROF") != nullptr; return e; }
+    GappedProf() : on(enabled()), mark(on ? now() : 0) {}
+    void lap(double& acc) { if (!on) return; const double t = now(); acc += t - mark; mark = t; }
+    struct Scope {
+        double* const acc; const double t0;
+        Scope(const GappedProf& p, double& a) : acc(p.on ? &a : nullptr), t0(p.on ? now() : 0) {}
+        ~Scope() { if (acc) *acc += now() - t0; }
+    };
+    void print(u64 rounds) const
+    {
+        if (on) fprintf(stderr, "[lzgpu hostprof] gapped: sort %.2f ms, windows %.2f ms, DP launches %.2f ms, pre-build %.2f ms, commit %.2f ms (neighbours %.2f, validity %.2f, build %.2f: of which neighbours of the new alignment + lists %.2f [align_left_right %.2f], coverage of deferred anchors %.2f) (%u rounds)\n",
+                        sort, window, exec, prebuild, commit, c_lr, c_chk, c_build, c_ins, c_alr, c_cov, (unsigned)rounds);
+    }
+};
+
+struct Triv { u32 lo1, lo2, len; };                            // a trivial alignment: one diagonal piece
+struct Info { s32 s; u32 beg1, beg2, end1, end2; std::vector<u32> script; bool trivial = false; };   // what the output needs of an alignment (parallel to S.aligns)
+struct Entry { u32 anchor_ix; bool speculated; u32 near_slot; };   // near_slot: the selected anchor a deferred one was found near (its ext_l / ext_r slot)
+// A finished speculative DP pair stays usable across windows for as long as its validity
+// conditions hold against the alignments committed after the snapshot it ran against.
+struct Cached { u32 a1, a2; Neighbours nb; size_t n_snap; LzDpResult rl, rr; std::vector<u32> ol, orr; };
+// (indexed by anchor: the window scan looks every anchor up -- 3 x 10^5 per strand of the 200 Mbp pair, nearly all of them
+// misses -- and a hash table made that look-up the scan's whole cost: 15 of its 16 ms)
+struct AnchorCache {
+    std::vector<s32> ix; std::deque<Cached> pool; std::vector<s32> free_list;
+    explicit AnchorCache(size_t n) : ix(n, -1) {}
+    Cached* find(u32 j) { return ix[j] >= 0 ? &pool[(size_t)ix[j]] : nullptr; }
+    void erase(u32 j) { if (ix[j] >= 0) { pool[(size_t)ix[j]] = Cached(); free_list.push_back(ix[j]); ix[j] = -1; } }
+    Cached& emplace(u32 j, Cached&& c)
+    {
+        s32 k;
+        if (!free_list.empty()) { k = free_list.back(); free_list.pop_back(); pool[(size_t)k] = std::move(c); }
+        else { k = (s32)pool.size(); pool.push_back(std::move(c)); }
+        ix[j] = k; return pool[(size_t)k];
+    }
+};
+struct Prebuilt { Built b; std::vector<LzDpSeg> segs; bool have = false; };   // what the commit of a speculated entry would build
+struct Chosen { s64 dg, a1; u32 ext; };                        // a selected anchor of this window, and its slot in ext_l / ext_r
+struct Member { u32 e, pos1, pos2; };                          // a deferred entry (index into entries) and its anchor
+
+// Which anchors of a window are worth a speculative DP.  Most anchors lie on the alignment an
+// earlier (better) anchor is about to produce -- the reference drops them in msp_left_right
+// without running a DP (98.5 % on the 10 Mbp pair).  An anchor within
+// NEAR_DIAG diagonals and NEAR_POS target bases of an anchor already selected in this window
+// is therefore deferred: when the commit pass reaches it, it is either on a committed
+// alignment (skipped, as in the reference) or it starts the next window.  This only steers
+// what is speculated; what is committed is decided by the checks of the commit pass.
+static const s64 NEAR_DIAG = 1500, NEAR_POS = 60000, TIGHT_DIAG = 300;
+static const u32 INSURE = 256;
+
+// What one window owns: filled by the scan, read by the launch, the pre-build and the commit pass, cleared by the next scan.
+struct GappedWindow {
+    std::vector<Entry> entries;                                // the anchors of the window that are not on an alignment, in commit order
+    std::vector<u32> fresh;                                    // anchors launched in this round
+    std::vector<LzDpJob> jobs;                                 // their DPs: jobs[2k] left, jobs[2k + 1] right of fresh[k]
+    u32 scan_end = 0;                                          // the first anchor the scan did not reach
+    // cells of NEAR_DIAG diagonals, directly indexed (diagonals run from -qlen to tlen); `touched` lists the cells in use
+    std::vector<std::vector<Chosen>> chosen_grid; std::vector<u32> touched;
+    // How far the deferred anchors near a selected one reach on either side of it: a guess at the rows its two DPs
+    // will sweep (the anchors an alignment swallows line up along it).  Only the launch order uses it -- a launch
+    // lasts as long as its longest DP, so the long ones should be among the first resident.
+    std::vector<u32> ext_l, ext_r;
+    std::unordered_map<u32, u32> ext_of;                       // anchor index -> slot
+    std::vector<std::vector<Member>> slot_members;             // the deferred entries found near a slot's selected anchor
+    std::vector<std::pair<s64, s64>> slot_anchor;              // LZGPU_HOSTPROF: (diagonal, pos1) of a slot's selected anchor
+    std::vector<u32> spec_of, spec_list;                       // entry -> its place in prebuilt / the speculated entries
+    std::vector<Prebuilt> prebuilt;                            // per SPECULATED entry of the window
+    std::vector<u8> covered;                                   // the deferred entry lies on its slot's alignment (mark_covered; counts once that is committed)
+    std::vector<s32> slot_align;                               // alignment committed for a selected anchor of this window
+    void clear()
+    {
+        jobs.clear(); entries.clear(); fresh.clear(); ext_l.clear(); ext_r.clear(); ext_of.clear(); slot_anchor.clear();
+        for (auto& v : slot_members) v.clear();
+        for (u32 t : touched) chosen_grid[t].clear();
+        touched.clear();
+    }
+};
+
+static u32 helper_min_anchors() { static const u32 v = []() { const char* e = getenv("LZGPU_HELPER_MIN_ANCHORS"); return (u32)(e ? atoi(e) : 20000); }(); return v; }   // (tests: 0)
+// (three helpers for a 50 Mbp strand's 79 k anchors; seven from 150 k anchors on -- a 200 Mbp strand has 300 k, 9 k alignments to build per round:
+// gapped stage 0.230-0.245 -> 0.222-0.231 s; LZGPU_HELPERS fixes the number)
+static u32 helper_count(u32 n_anchors)
 {
-    out.clear(); out_ops.clear();
-    memset(&st, 0, sizeof(st));
-    // The trivial alignments the reference puts in front of the anchors (src/gapped_extend.c:1118-1290):
-    //  * neither sequence partitioned: the self-alignment when identical_sequences says so (:1886-1933: dna_toupper() of
-    //    the bytes equal, same strand flags);
-    //  * seq1 partitioned, seq2 not: ONE, for the first partition of seq1 that is seq2 (identical_partition_of_sequence,
-    //    :2034-2113);
-    //  * both partitioned: one per partition pair (k, k) when ALL pairs are identical (identical_partitioned_sequences,
-    //    :1952-1997).
-    // With inhibitTrivial and partitions but no such "partitioned triviality" the reference instead drops, at output time,
-    // alignments that cover a whole partition pair of equal NAME (delayedCheckForTrivial, :1485-1545): names do not cross
-    // this ABI, so a result that holds a candidate for that test is declined at the end (below).
-    struct Triv { u32 lo1, lo2, len; };
-    std::vector<Triv> triv;
-    bool delayed_check = false;
-    auto n_parts = [](const u32* sep, u32 n_sep) { return sep ? (n_sep ? n_sep - 1 : 0u) : 1u; };
-    auto part_of = [&](const u32* sep, u32 k, u32 whole, u32& lo, u32& hi) { if (sep) { lo = sep[k] + 1; hi = sep[k + 1]; } else { lo = 0; hi = whole; } };
+    static const u32 helper_env = []() { const char* e = getenv("LZGPU_HELPERS"); const int v = e ? atoi(e) : 0; return (u32)(v > 0 ? v : 0); }();
+    const u32 helper_n = helper_env ? helper_env : (n_anchors >= 150000u ? 7u : 3u);
+    return n_anchors >= helper_min_anchors() ? helper_n : 0u;   // (small problems -- tweener windows -- stay on their own thread)
+}
+
+// What lives across the windows of one lzh_gapped_extend call.
+struct GappedPass {
+    const LzGappedParams& G; LzDpExecutor& exec; lz_segment* const anchors; const u32 n_anchors; LzGappedStats& st;
+    const u32 W;                                               // anchors speculated per round
+    const s64 cell_lo;                                         // the grid cell of the lowest diagonal
+    LzHostSnapshot S;
+    std::vector<Info> info;                                    // parallel to S.aligns
+    AnchorCache cache;
+    // the alignment committed for the selected anchor a deferred anchor was found near, remembered across windows:
+    // when a window is cut, the anchors behind the cut are scanned again and most of them lie on that alignment
+    std::vector<s32> near_align;
+    std::vector<LzDpResult> res; std::vector<std::vector<u32>> ops;     // a launch's results, until they are in the cache
+    u32 next = 0;                                              // the first anchor not committed, skipped or dropped yet
+    u64 paired_bases = 0;
+    ForkJoin helpers;
+    GappedWindow w;
+    GappedProf prof;
+
+    // (built after the anchors are sorted: `pr` holds the sort's lap, and what is set up here counts into the first window's)
+    GappedPass(const LzGappedParams& g, LzDpExecutor& x, lz_segment* a, u32 n, LzGappedStats& s, const GappedProf& pr)
+        : G(g), exec(x), anchors(a), n_anchors(n), st(s), W(g.window ? g.window : 1024), cell_lo(-(s64)(g.qlen / NEAR_DIAG) - 2),
+          cache(n), near_align(n, -1), helpers(helper_count(n)), prof(pr)
+    {
+        w.chosen_grid.resize((size_t)((s64)(G.tlen / NEAR_DIAG) + 2 - cell_lo + 1));
+    }
+
+    // One more alignment in the snapshot: its pieces, its record (`m`: ends and neighbours are the caller's), what the
+    // output needs of it, and its place in the two orders.
+    void append_alignment(const LzDpSeg* segs, size_t n_segs, LzDpAlign m, Info&& in)
+    {
+        m.first_seg = (s32)S.segs.size(); m.last_seg = m.first_seg + (s32)n_segs - 1;
+        S.segs.insert(S.segs.end(), segs, segs + n_segs);
+        S.aligns.push_back(m);
+        info.push_back(std::move(in));
+        insert_align(S, (s32)S.aligns.size() - 1);
+    }
+
+    // a trivial alignment bounds every anchor from the start, :1152-1290 (one diagonal segment; its score saturates
+    // at bestPossibleScore and is raised to the threshold "so it won't be discarded")
+    void add_trivial(const Triv& tv)
+    {
+        s32 sc = 0;
+        for (u32 i = 0; i < tv.len; i++) {
+            const s32 wt = G.sub[(u32)fold_case(G.t[tv.lo1 + i]) * 256 + fold_case(G.q[tv.lo2 + i])];
+            if (sc == 0x7FFFFFFF) ;
+            else if (wt <= 0 || sc < 0x7FFFFFFF - wt) sc += wt;
+            else sc = 0x7FFFFFFF;
+        }
+        LzDpAlign m; memset(&m, 0, sizeof(m));
+        m.pos1 = tv.lo1; m.pos2 = tv.lo2; m.end1 = tv.lo1 + tv.len - 1; m.end2 = tv.lo2 + tv.len - 1;
+        m.left_align1 = m.right_align1 = m.left_align2 = m.right_align2 = -1;
+        m.left_seg1 = m.right_seg1 = m.left_seg2 = m.right_seg2 = -1;
+        LzDpSeg g; g.b1 = m.pos1; g.b2 = m.pos2; g.e1 = m.end1; g.e2 = m.end2; g.type = LZ_DIAG_SEG;
+        Info in; in.s = sc < G.score_thresh ? G.score_thresh : sc; in.beg1 = tv.lo1 + 1; in.beg2 = tv.lo2 + 1; in.end1 = tv.lo1 + tv.len; in.end2 = tv.lo2 + tv.len; in.trivial = true;
+        for (u32 left = tv.len; left; ) { const u32 n = left < 0x3FFFFFFFu ? left : 0x3FFFFFFFu; in.script.push_back((n << 2) | 3u); left -= n; }   // edit_script_sub
+        append_alignment(&g, 1, m, std::move(in));
+    }
+
+    // ---- scan: the speculation window against the current snapshot
+
+    // (the selected anchors are kept in cells of NEAR_DIAG diagonals: a near one is in the anchor's
+    // cell or one next to it -- a window scans up to 64 K anchors against up to 1 K selected ones)
+    static s64 cell_of(s64 dg) { return (dg >= 0 ? dg : dg - (NEAR_DIAG - 1)) / NEAR_DIAG; }
+
+    // Is the anchor near a selected one?  0 = not near, 1 = near (loose), 2 = near and almost on the same diagonal (tight);
+    // near_slot: that anchor's slot, whose extent grows to reach this one
+    int near_selected(s64 dg, u32 a1, u32& near_slot)
+    {
+        int near = 0;
+        const s64 cell = cell_of(dg);
+        for (s64 cc = cell - 1; cc <= cell + 1 && near < 2; cc++) {
+            const s64 gi = cc - cell_lo;
+            if (gi < 0 || gi >= (s64)w.chosen_grid.size()) continue;
+            for (auto& c : w.chosen_grid[(size_t)gi])
+                if (c.dg - dg <= NEAR_DIAG && dg - c.dg <= NEAR_DIAG &&
+                    c.a1 - (s64)a1 <= NEAR_POS && (s64)a1 - c.a1 <= NEAR_POS) {
+                    near = (c.dg - dg <= TIGHT_DIAG && dg - c.dg <= TIGHT_DIAG) ? 2 : (near < 1 ? 1 : near);
+                    near_slot = c.ext;
+                    if ((s64)a1 < c.a1) { const u32 d = (u32)(c.a1 - (s64)a1); if (d > w.ext_l[c.ext]) w.ext_l[c.ext] = d; }
+                    else                { const u32 d = (u32)((s64)a1 - c.a1); if (d > w.ext_r[c.ext]) w.ext_r[c.ext] = d; }
+                    if (near == 2) break;
+                }
+        }
+        return near;
+    }
+
+    // anchor j becomes a selected anchor of the window: a slot, a place in the grid, a speculated entry
+    void select_anchor(u32 j, s64 dg, u32 a1)
+    {
+        const u32 slot = (u32)w.ext_l.size();
+        w.ext_of[j] = slot;
+        { const size_t gi = (size_t)(cell_of(dg) - cell_lo); if (w.chosen_grid[gi].empty()) w.touched.push_back((u32)gi); w.chosen_grid[gi].push_back({ dg, (s64)a1, slot }); }
+        w.ext_l.push_back(0); w.ext_r.push_back(0);
+        if (w.slot_members.size() < w.ext_l.size()) w.slot_members.emplace_back();
+        if (prof.on) w.slot_anchor.push_back({ dg, (s64)a1 });
+        w.entries.push_back({ j, true, slot });
+    }
+
+    // the two one-sided DPs of anchor j against the snapshot, and the cache entry their results will go to
+    int add_jobs(u32 j, u32 a1, u32 a2, const Neighbours& nb)
+    {
+        // get_above_below, :4043-4059
+        s32 below, above;
+        above_below(S, a1, below, above);
+        // the partition holding the anchor bounds its extension, :1356-1372 / ydrop_align :2515-2531
+        u32 low1, high1, low2, high2;
+        if (!partition_limits(G.sep1, G.n_sep1, a1, G.tlen, low1, high1) || !partition_limits(G.sep2, G.n_sep2, a2, G.qlen, low2, high2)
+            || a1 + 1 > high1 || a2 + 1 > high2) return LZGPU_ERR_STATE;
+        LzDpJob L; memset(&L, 0, sizeof(L));
+        L.anchor1 = a1; L.anchor2 = a2; L.reversed = 1; L.M = a1 + 1 - low1; L.N = a2 + 1 - low2;
+        L.left_align = nb.la; L.left_seg = nb.ls; L.right_align = nb.ra; L.right_seg = nb.rs;
+        L.list_start = below;
+        LzDpJob R = L;
+        R.reversed = 0; R.M = high1 - (a1 + 1); R.N = high2 - (a2 + 1); R.list_start = above;
+        w.jobs.push_back(L); w.jobs.push_back(R);
+        Cached cr; cr.a1 = a1; cr.a2 = a2; cr.nb = nb; cr.n_snap = S.aligns.size();
+        cache.emplace(j, std::move(cr));
+        w.fresh.push_back(j);
+        return 0;
+    }
+
+    int scan_window()
+    {
+        w.clear();
+        u32 insured = 0;
+        u32 j = next;
+        const u32 scan_limit = 64 * W;
+        for (; j < n_anchors && w.fresh.size() < W && w.entries.size() < scan_limit; j++) {
+            const u32 a1 = anchors[j].pos1, a2 = anchors[j].pos2;
+            Neighbours nb;
+            if (near_align[j] >= 0 && on_alignment(S, S.aligns[near_align[j]], a1, a2)) { cache.erase(j); continue; }
+            int ok = msp_left_right(S, a1, a2, nb);
+            if (ok < 0) return LZGPU_ERR_STATE;
+            if (ok == 0) { cache.erase(j); continue; }         // on an earlier alignment: gone for good
+            const s64 dg = (s64)a1 - (s64)a2;
+            const bool hit = cache.find(j) != nullptr;
+            if (!hit) {
+                u32 near_slot = 0;
+                int near = near_selected(dg, a1, near_slot);
+                // a loosely near anchor is usually on the selected anchor's alignment too, but when it is not it
+                // costs a whole extra round for one DP: a bounded number of them is speculated anyway
+                if (near == 1 && insured < INSURE) { insured++; near = 0; }
+                if (near) { w.slot_members[near_slot].push_back({ (u32)w.entries.size(), a1, a2 }); w.entries.push_back({ j, false, near_slot }); continue; }
+            }
+            select_anchor(j, dg, a1);
+            if (hit) continue;                                 // result of an earlier round, re-validated at commit
+            if (int rc = add_jobs(j, a1, a2, nb)) return rc;
+        }
+        w.scan_end = j;
+        prof.lap(prof.window);
+        if (prof.on && st.rounds >= 1) { fprintf(stderr, "[lzgpu hostprof] round %u speculates anchors (rank:score):", (unsigned)st.rounds + 1); for (size_t k = 0; k < w.fresh.size() && k < 12; k++) fprintf(stderr, " %u:%d", w.fresh[k], anchors[w.fresh[k]].s); fprintf(stderr, " of %u entries\n", (unsigned)w.entries.size()); }
+        return 0;
+    }
+
+    // ---- launch: the window's DPs in one call of the executor; their results go to the cache
+    int launch()
+    {
+        for (size_t k = 0; k < w.fresh.size(); k++) {          // (the extents kept growing while the window was scanned)
+            const u32 e = w.ext_of[w.fresh[k]];
+            w.jobs[2 * k].est_rows = w.ext_l[e]; w.jobs[2 * k + 1].est_rows = w.ext_r[e];
+        }
+        if (!w.jobs.empty()) {
+            res.assign(w.jobs.size(), LzDpResult());
+            ops.assign(w.jobs.size(), std::vector<u32>());
+            int rc = exec.run(S, w.jobs, res, ops);
+            if (rc) return rc;
+            for (size_t k = 0; k < w.fresh.size(); k++) {
+                Cached& cr = *cache.find(w.fresh[k]);
+                cr.rl = res[2 * k]; cr.rr = res[2 * k + 1];
+                cr.ol.swap(ops[2 * k]); cr.orr.swap(ops[2 * k + 1]);
+            }
+            for (const LzDpResult& r : res) st.dp_rows += r.max_row;
+        }
+        st.rounds++; st.dp_runs += w.jobs.size();
+        prof.lap(prof.exec);
+        return 0;
+    }
+
+    // ---- pre-build: what a commit builds from a DP pair -- the spliced script, its end trimming and rescoring, the pieces -- depends on
+    // the pair alone: done for every speculated entry of the window up front, on the helpers (splice_and_trim walks both
+    // sequences along the whole alignment: 2/3 of the serial pass it is taken out of)
+
+    // Which of the deferred anchors found near a selected anchor lie on the alignment built for it: "on an alignment" needs no
+    // more than one witness (:3953-4028), so the commit pass reads one flag per deferred anchor once that alignment is committed.
+    // One slot, one writer: a slot's members belong to the one speculated entry that opened the slot, and an entry's alignment is
+    // built once -- by a helper of the pre-build burst, or by the commit pass when the burst had nothing to build it from -- so no
+    // two threads ever write the same flag, and nobody reads one before the burst has ended.
+    void mark_covered(const Entry& en, const std::vector<LzDpSeg>& segs)
+    {
+        if (en.near_slot >= w.slot_members.size()) return;
+        for (const Member& mb : w.slot_members[en.near_slot]) if (on_pieces(segs, mb.pos1, mb.pos2)) w.covered[mb.e] = 1;
+    }
+    void build_alignment(const Cached& sp, const Entry& en, Prebuilt& pb)
+    {
+        splice_and_trim(G, sp.a1, sp.a2, sp.rl, sp.ol, sp.rr, sp.orr, pb.b);
+        format_segments(pb.b, pb.segs);
+        pb.have = true;
+        mark_covered(en, pb.segs);
+    }
+    void prebuild()
+    {
+        w.spec_of.assign(w.entries.size(), 0xFFFFFFFFu);
+        w.spec_list.clear();
+        for (size_t e = 0; e < w.entries.size(); e++) if (w.entries[e].speculated) { w.spec_of[e] = (u32)w.spec_list.size(); w.spec_list.push_back((u32)e); }
+        w.prebuilt.clear(); w.prebuilt.resize(w.spec_list.size());
+        w.covered.assign(w.entries.size(), 0);
+        const std::function<void(size_t, size_t)> build = [&](size_t lo, size_t hi) {
+            for (size_t k = lo; k < hi; k++) {
+                const Entry& en = w.entries[w.spec_list[k]];
+                const Cached* sp = cache.find(en.anchor_ix);   // (concurrent look-ups only: nothing is inserted or erased here)
+                if (sp != nullptr) build_alignment(*sp, en, w.prebuilt[k]);
+            }
+        };
+        helpers.begin_burst();
+        helpers.run(w.spec_list.size(), helper_min_anchors() ? 16 : 1, build);
+        helpers.end_burst();
+        prof.lap(prof.prebuild);
+    }
+
+    // ---- commit in the reference's order
+
+    // Is the cached DP pair the one the reference would run now?
+    // (a) same neighbour segments at the anchor as when it ran and nothing committed since
+    //     touches what it explored: identical inputs wherever the DP looked;
+    // (b) or no alignment at all touches what it explored: every bound (L, R, masks) the
+    //     reference would track lies outside the band on every row, whichever neighbours it
+    //     starts from, so the DP is the unconstrained one.
+    bool still_valid(const Cached& sp, const Neighbours& nb) const
+    {
+        const LzDpResult& rl = sp.rl; const LzDpResult& rr = sp.rr;
+        // Rectangles the two one-sided DPs explored, +-2 cells (target rows x query columns):
+        const s64 lr0 = (s64)sp.a1 + 1 - (s64)rl.max_row - 2, lr1 = (s64)sp.a1 + 2;
+        const s64 lc0 = (s64)sp.a2 + 1 - (s64)rl.max_col - 2, lc1 = (s64)sp.a2 + 1 - (s64)rl.min_col + 2;
+        const s64 rr0 = (s64)sp.a1 - 2, rr1 = (s64)sp.a1 + (s64)rr.max_row + 2;
+        const s64 rc0 = (s64)sp.a2 + (s64)rr.min_col - 2, rc1 = (s64)sp.a2 + (s64)rr.max_col + 2;
+        // (only alignments that overlap the two rectangles' rows can touch them: obi is ordered by pos1 and obi_maxend is
+        // the running maximum of end1, so they are a stretch of obi found by bisection -- walking every alignment
+        // committed since the snapshot was quadratic, 10 ms per strand at the north star's size)
+        const Rect2 rects = { lr0, lr1, lc0, lc1, rr0, rr1, rc0, rc1 };
+        const bool same = nb.la == sp.nb.la && nb.ls == sp.nb.ls && nb.ra == sp.nb.ra && nb.rs == sp.nb.rs;
+        return !touched_since(S, same ? sp.n_snap : 0, rects);
+    }
+
+    // one entry of the window; cut: the window ends here and `next` is the anchor the next one starts from
+    int commit_entry(size_t e, bool& cut)
+    {
+        const Entry& en = w.entries[e];
+        const u32 aix = en.anchor_ix;
+        Neighbours nb;
+        // A deferred anchor nearly always lies on the alignment of the selected anchor it was found near: that was tested for
+        // all of a slot's deferred anchors at once when the slot's alignment was built (mark_covered); one flag to read here.
+        // (A deferred anchor has no cached DP: nothing to erase.)
+        if (w.covered[e] && !en.speculated && en.near_slot < w.slot_align.size() && w.slot_align[en.near_slot] >= 0) return 0;
+        int ok;
+        { GappedProf::Scope t(prof, prof.c_lr); ok = msp_left_right(S, anchors[aix].pos1, anchors[aix].pos2, nb); }
+        if (ok < 0) return LZGPU_ERR_STATE;
+        if (ok == 0) { cache.erase(aix); return 0; }           // lies on an alignment committed meanwhile
+        if (!en.speculated) {                                  // needs a DP: head of the next window
+            // (On the bench pair every strand has one or two of these: an anchor a few diagonals beside the long
+            // alignment of the selected anchor it was found near, 8 kbp along it.  Its DP is bounded by that very
+            // alignment, so it cannot be launched before the alignment exists: the second round is inherent.  A rule
+            // that also speculated the first anchor beyond every 1.5 kbp gap in the run of deferred anchors found
+            // nothing to add here and cost 5 ms of sorting -- not kept.)
+            if (prof.on && en.near_slot < w.slot_anchor.size())
+                fprintf(stderr, "[lzgpu hostprof] window cut at anchor %u (score %d): deferred near a selected anchor %lld diagonals and %lld bases away, not on its alignment\n",
+                        aix, anchors[aix].s, (long long)((s64)anchors[aix].pos1 - (s64)anchors[aix].pos2 - w.slot_anchor[en.near_slot].first),
+                        (long long)((s64)anchors[aix].pos1 - w.slot_anchor[en.near_slot].second));
+            next = aix; cut = true; return 0;
+        }
+        const Cached& sp = *cache.find(aix);
+        bool same;
+        { GappedProf::Scope t(prof, prof.c_chk); same = still_valid(sp, nb); }
+        GappedProf::Scope t_build(prof, prof.c_build);
+        if (!same) { cache.erase(aix); next = aix; cut = true; st.reruns++; return 0; }
+        st.anchors_extended++;
+        st.dp_cells += sp.rl.cells + sp.rr.cells;
+        st.truncated += (sp.rl.truncated ? 1 : 0) + (sp.rr.truncated ? 1 : 0);     // :3640-3661: the reference warns on stderr
+        Prebuilt& pb = w.prebuilt[w.spec_of[e]];
+        if (!pb.have) build_alignment(sp, en, pb);
+        Built& b = pb.b;
+        const std::vector<LzDpSeg>& segs = pb.segs;
+        cache.erase(aix);
+        if (segs.empty()) return 0;                            // empty alignment, :1401-1405
+        if (!G.all_bounds && b.s < G.score_thresh) return 0;   // :1419-1429
+        {
+            GappedProf::Scope t_ins(prof, prof.c_ins);
+            LzDpAlign m; memset(&m, 0, sizeof(m));
+            m.pos1 = b.start1; m.pos2 = b.start2; m.end1 = b.stop1; m.end2 = b.stop2;
+            { GappedProf::Scope t_alr(prof, prof.c_alr); align_left_right(S, m); }
+            Info in; in.s = b.s; in.beg1 = b.start1 + 1; in.beg2 = b.start2 + 1; in.end1 = b.stop1 + 1; in.end2 = b.stop2 + 1;
+            in.script.swap(b.script);
+            append_alignment(segs.data(), segs.size(), m, std::move(in));
+        }
+        GappedProf::Scope t_cov(prof, prof.c_cov);
+        if (en.near_slot < w.slot_align.size()) w.slot_align[en.near_slot] = (s32)S.aligns.size() - 1;
+        if (G.max_paired_bases) {                              // count_paired_bases, :5695-5706; the limit test of :1441-1459
+            for (const LzDpSeg& g : segs) if (g.type == LZ_DIAG_SEG) paired_bases += (u64)g.e1 + 1 - g.b1;
+            if (paired_bases > G.max_paired_bases) return LZGPU_NH_PAIRED_LIMIT;
+        }
+        return 0;
+    }
+
+    int commit()
+    {
+        bool cut = false;
+        w.slot_align.assign(w.ext_l.size(), -1);
+        for (size_t e = 0; e < w.entries.size() && !cut; e++)
+            if (int rc = commit_entry(e, cut)) return rc;
+        if (cut) for (const Entry& en : w.entries)             // for the scan of the next window
+            if (!en.speculated && en.near_slot < w.slot_align.size()) near_align[en.anchor_ix] = w.slot_align[en.near_slot];
+        if (!cut) next = w.scan_end;
+        prof.lap(prof.commit);
+        return 0;
+    }
+
+    // ---- inhibitTrivial's test by sequence name (:1485-1545) cannot be made here: is there a candidate for it (one diagonal
+    // piece covering a whole partition pair of equal length, base for base the same) among the alignments?
+    bool holds_trivial_candidate() const
+    {
+        for (s32 ai : S.obi) {
+            const LzDpAlign& al = S.aligns[ai];
+            if (info[ai].s < G.score_thresh || al.first_seg != al.last_seg || S.segs[al.first_seg].type != LZ_DIAG_SEG) continue;
+            u32 lo1, hi1, lo2, hi2;
+            if (!partition_limits(G.sep1, G.n_sep1, al.pos1, G.tlen, lo1, hi1) || !partition_limits(G.sep2, G.n_sep2, al.pos2, G.qlen, lo2, hi2)) continue;
+            if (hi1 - lo1 != hi2 - lo2 || al.end1 + 1 - al.pos1 != hi1 - lo1) continue;
+            if (memcmp(G.t + al.pos1, G.q + al.pos2, al.end1 + 1 - al.pos1) == 0) return true;
+        }
+        return false;
+    }
+
+    // ---- output in increasing start order (orderBegInc), :1475-1566
+    void emit(std::vector<lz_align>& out, std::vector<u32>& out_ops) const
+    {
+        for (s32 ai : S.obi) {
+            const Info& in = info[ai];
+            if (in.s < G.score_thresh) continue;
+            if (G.inhibit_trivial && in.trivial) continue;            // :1483
+            lz_align a; a.beg1 = in.beg1; a.beg2 = in.beg2; a.end1 = in.end1; a.end2 = in.end2; a.s = in.s;
+            a.script_len = (u32)in.script.size(); a.script_off = (u32)out_ops.size();
+            out_ops.insert(out_ops.end(), in.script.begin(), in.script.end());
+            out.push_back(a);
+        }
+    }
+};
+
+static int check_separators(const LzGappedParams& G)
+{
     if (G.sep1) for (u32 k = 0; k + 1 < G.n_sep1; k++) if (G.sep1[k + 1] > G.tlen || G.sep1[k] + 1 > G.sep1[k + 1]) return LZGPU_ERR_ARG;
     if (G.sep2) for (u32 k = 0; k + 1 < G.n_sep2; k++) if (G.sep2[k + 1] > G.qlen || G.sep2[k] + 1 > G.sep2[k + 1]) return LZGPU_ERR_ARG;
+    return 0;
+}
+
+// The trivial alignments the reference puts in front of the anchors (src/gapped_extend.c:1118-1290):
+//  * neither sequence partitioned: the self-alignment when identical_sequences says so (:1886-1933: dna_toupper() of
+//    the bytes equal, same strand flags);
+//  * seq1 partitioned, seq2 not: ONE, for the first partition of seq1 that is seq2 (identical_partition_of_sequence,
+//    :2034-2113);
+//  * both partitioned: one per partition pair (k, k) when ALL pairs are identical (identical_partitioned_sequences,
+//    :1952-1997).
+// With inhibitTrivial and partitions but no such "partitioned triviality" the reference instead drops, at output time,
+// alignments that cover a whole partition pair of equal NAME (delayedCheckForTrivial, :1485-1545): names do not cross
+// this ABI, so a result that holds a candidate for that test is declined at the end (delayed_check).
+static int trivial_alignments(const LzGappedParams& G, std::vector<Triv>& triv, bool& delayed_check)
+{
+    auto n_parts = [](const u32* sep, u32 n_sep) { return sep ? (n_sep ? n_sep - 1 : 0u) : 1u; };
+    auto part_of = [&](const u32* sep, u32 k, u32 whole, u32& lo, u32& hi) { if (sep) { lo = sep[k] + 1; hi = sep[k + 1]; } else { lo = 0; hi = whole; } };
+    delayed_check = false;
     if (!G.sep1 && !G.sep2) {
         if (!G.strands_differ && G.tlen == G.qlen && G.tlen > 0 && same_bases(G.t, G.q, G.tlen)) triv.push_back({ 0u, 0u, G.tlen });
     } else if (G.sep1 && !G.sep2) {
@@ -453,346 +896,38 @@ int lzh_gapped_extend(const LzGappedParams& G, LzDpExecutor& exec, lz_segment* a
             }
         delayed_check = G.inhibit_trivial && !all;
     } else delayed_check = G.inhibit_trivial;                             // (seq2 alone partitioned: no partitioned triviality, :1124-1147)
-    if (G.gap_extend <= 0) return LZGPU_NH_UNSUPPORTED;
+    return 0;
+}
 
-    // LZGPU_HOSTPROF=1: where the host time of the stage goes
-    static const bool prof = getenv("LZGPU_HOSTPROF") != nullptr;
-    double t_sort = 0, t_window = 0, t_exec = 0, t_prebuild = 0, t_commit = 0, t_c_lr = 0, t_c_chk = 0, t_c_build = 0, t_c_alr = 0, t_c_ins = 0, t_c_cov = 0;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_mark = now();
-    auto lap = [&](double& acc) { const double t = now(); acc += t - t_mark; t_mark = t; };
+}   // namespace
+
+int lzh_gapped_extend(const LzGappedParams& G, LzDpExecutor& exec, lz_segment* anchors, u32 n_anchors,
+                      std::vector<lz_align>& out, std::vector<u32>& out_ops, LzGappedStats& st)
+{
+    out.clear(); out_ops.clear();
+    memset(&st, 0, sizeof(st));
+    int rc;
+    std::vector<Triv> triv;
+    bool delayed_check;
+    if ((rc = check_separators(G))) return rc;
+    if ((rc = trivial_alignments(G, triv, delayed_check))) return rc;
+    if (G.gap_extend <= 0) return LZGPU_NH_UNSUPPORTED;
+    GappedProf prof;
     lzh_sort4(anchors, anchors + n_anchors, seg_before);       // batched_segments, :1675
     st.anchors = n_anchors;
-    lap(t_sort);
-
-    LzHostSnapshot S;
-    struct Info { s32 s; u32 beg1, beg2, end1, end2; std::vector<u32> script; bool trivial = false; };
-    std::vector<Info> info;                                    // parallel to S.aligns
-    for (const Triv& tv : triv) {
-        // a trivial alignment bounds every anchor from the start, :1152-1290 (one diagonal segment; its score saturates
-        // at bestPossibleScore and is raised to the threshold "so it won't be discarded")
-        s32 sc = 0;
-        for (u32 i = 0; i < tv.len; i++) {
-            u8 a = G.t[tv.lo1 + i], b = G.q[tv.lo2 + i];
-            if (a >= 'a' && a <= 'z') a -= 32;
-            if (b >= 'a' && b <= 'z') b -= 32;
-            const s32 w = G.sub[(u32)a * 256 + b];
-            if (sc == 0x7FFFFFFF) ;
-            else if (w <= 0 || sc < 0x7FFFFFFF - w) sc += w;
-            else sc = 0x7FFFFFFF;
-        }
-        LzDpAlign m; memset(&m, 0, sizeof(m));
-        m.pos1 = tv.lo1; m.pos2 = tv.lo2; m.end1 = tv.lo1 + tv.len - 1; m.end2 = tv.lo2 + tv.len - 1;
-        m.first_seg = m.last_seg = (s32)S.segs.size();
-        m.left_align1 = m.right_align1 = m.left_align2 = m.right_align2 = -1;
-        m.left_seg1 = m.right_seg1 = m.left_seg2 = m.right_seg2 = -1;
-        LzDpSeg g; g.b1 = m.pos1; g.b2 = m.pos2; g.e1 = m.end1; g.e2 = m.end2; g.type = LZ_DIAG_SEG;
-        S.segs.push_back(g); S.aligns.push_back(m);
-        Info in; in.s = sc < G.score_thresh ? G.score_thresh : sc; in.beg1 = tv.lo1 + 1; in.beg2 = tv.lo2 + 1; in.end1 = tv.lo1 + tv.len; in.end2 = tv.lo2 + tv.len; in.trivial = true;
-        for (u32 left = tv.len; left; ) { const u32 n = left < 0x3FFFFFFFu ? left : 0x3FFFFFFFu; in.script.push_back((n << 2) | 3u); left -= n; }   // edit_script_sub
-        info.push_back(std::move(in));
-        insert_align(S, (s32)S.aligns.size() - 1);
+    prof.lap(prof.sort);
+    GappedPass p(G, exec, anchors, n_anchors, st, prof);
+    for (const Triv& tv : triv) p.add_trivial(tv);
+    while (p.next < n_anchors) {
+        if ((rc = p.scan_window())) return rc;
+        if (p.w.entries.empty()) break;                        // every anchor left is on an alignment
+        if ((rc = p.launch())) return rc;
+        p.prebuild();
+        if ((rc = p.commit())) return rc;
     }
-
-    const u32 W = G.window ? G.window : 1024;
-    u64 paired_bases = 0;
-    static const u32 helper_min = []() { const char* e = getenv("LZGPU_HELPER_MIN_ANCHORS"); return (u32)(e ? atoi(e) : 20000); }();   // (tests: 0)
-    // (three helpers for a 50 Mbp strand's 79 k anchors; seven from 150 k anchors on -- a 200 Mbp strand has 300 k, 9 k alignments to build per round:
-    // gapped stage 0.230-0.245 -> 0.222-0.231 s; LZGPU_HELPERS fixes the number)
-    static const u32 helper_env = []() { const char* e = getenv("LZGPU_HELPERS"); const int v = e ? atoi(e) : 0; return (u32)(v > 0 ? v : 0); }();
-    const u32 helper_n = helper_env ? helper_env : (n_anchors >= 150000u ? 7u : 3u);
-    ForkJoin helpers(n_anchors >= helper_min ? helper_n : 0u); // (small problems -- tweener windows -- stay on their own thread)
-    // Which anchors of a window are worth a speculative DP.  Most anchors lie on the alignment an
-    // earlier (better) anchor is about to produce -- the reference drops them in msp_left_right
-    // without running a DP (98.5 % on the 10 Mbp pair).  An anchor within
-    // NEAR_DIAG diagonals and NEAR_POS target bases of an anchor already selected in this window
-    // is therefore deferred: when the commit pass reaches it, it is either on a committed
-    // alignment (skipped, as in the reference) or it starts the next window.  This only steers
-    // what is speculated; what is committed is decided by the checks below.
-    const s64 NEAR_DIAG = 1500, NEAR_POS = 60000, TIGHT_DIAG = 300;
-    const u32 INSURE = 256;
-    u32 next = 0;
-    std::vector<LzDpJob> jobs; std::vector<LzDpResult> res; std::vector<std::vector<u32>> ops;
-    struct Entry { u32 anchor_ix; bool speculated; u32 near_slot; };   // near_slot: the selected anchor a deferred one was found near (its ext_l / ext_r slot)
-    // A finished speculative DP pair stays usable across windows for as long as its validity
-    // conditions hold against the alignments committed after the snapshot it ran against.
-    struct Cached { u32 a1, a2; Neighbours nb; size_t n_snap; LzDpResult rl, rr; std::vector<u32> ol, orr; };
-    // (indexed by anchor: the window scan looks every anchor up -- 3 x 10^5 per strand of the 200 Mbp pair, nearly all of them
-    // misses -- and a hash table made that look-up the scan's whole cost: 15 of its 16 ms)
-    struct AnchorCache {
-        std::vector<s32> ix; std::deque<Cached> pool; std::vector<s32> free_list;
-        explicit AnchorCache(size_t n) : ix(n, -1) {}
-        Cached* find(u32 j) { return ix[j] >= 0 ? &pool[(size_t)ix[j]] : nullptr; }
-        void erase(u32 j) { if (ix[j] >= 0) { pool[(size_t)ix[j]] = Cached(); free_list.push_back(ix[j]); ix[j] = -1; } }
-        Cached& emplace(u32 j, Cached&& c)
-        {
-            s32 k;
-            if (!free_list.empty()) { k = free_list.back(); free_list.pop_back(); pool[(size_t)k] = std::move(c); }
-            else { k = (s32)pool.size(); pool.push_back(std::move(c)); }
-            ix[j] = k; return pool[(size_t)k];
-        }
-    } cache(n_anchors);
-    struct Prebuilt { Built b; std::vector<LzDpSeg> segs; bool have = false; };
-    std::vector<Prebuilt> prebuilt;                            // per SPECULATED entry of the window: what its commit would build
-    std::vector<u32> spec_of, spec_list;                       // entry -> its place in prebuilt / the speculated entries
-    std::vector<Entry> entries;
-    std::vector<u32> fresh;                                    // anchors launched in this round
-    // the alignment committed for the selected anchor a deferred anchor was found near, remembered across windows:
-    // when a window is cut, the anchors behind the cut are scanned again and most of them lie on that alignment
-    std::vector<s32> near_align(n_anchors, -1);
-    struct Chosen { s64 dg, a1; u32 ext; };                    // a selected anchor of this window, and its slot in ext_l / ext_r
-    // cells of NEAR_DIAG diagonals, directly indexed (diagonals run from -qlen to tlen); `touched` lists the cells in use
-    const s64 cell_lo = -(s64)(G.qlen / NEAR_DIAG) - 2;
-    std::vector<std::vector<Chosen>> chosen_grid((size_t)((s64)(G.tlen / NEAR_DIAG) + 2 - cell_lo + 1));
-    std::vector<u32> touched;
-    // How far the deferred anchors near a selected one reach on either side of it: a guess at the rows its two DPs
-    // will sweep (the anchors an alignment swallows line up along it).  Only the launch order uses it -- a launch
-    // lasts as long as its longest DP, so the long ones should be among the first resident.
-    std::vector<u32> ext_l, ext_r;
-    struct Member { u32 e, pos1, pos2; };                      // a deferred entry (index into entries) and its anchor
-    std::vector<std::vector<Member>> slot_members;             // the deferred entries found near a slot's selected anchor
-    std::vector<u8> covered;                                   // commit pass: the deferred entry lies on its slot's alignment (checked when that was committed)
-    std::unordered_map<u32, u32> ext_of;                       // anchor index -> slot
-    std::vector<std::pair<s64, s64>> slot_anchor;              // LZGPU_HOSTPROF: (diagonal, pos1) of a slot's selected anchor
-    while (next < n_anchors) {
-        // ---- speculation window against the current snapshot
-        jobs.clear(); entries.clear(); fresh.clear(); ext_l.clear(); ext_r.clear(); ext_of.clear(); slot_anchor.clear();
-        for (auto& v : slot_members) v.clear();
-        for (u32 t : touched) chosen_grid[t].clear();
-        touched.clear();
-        u32 insured = 0;
-        u32 j = next;
-        const u32 scan_limit = 64 * W;
-        const size_t n_snap = S.aligns.size();
-        for (; j < n_anchors && fresh.size() < W && entries.size() < scan_limit; j++) {
-            const u32 a1 = anchors[j].pos1, a2 = anchors[j].pos2;
-            Neighbours nb;
-            if (near_align[j] >= 0 && on_alignment(S, S.aligns[near_align[j]], a1, a2)) { cache.erase(j); continue; }
-            int ok = msp_left_right(S, a1, a2, nb);
-            if (ok < 0) return LZGPU_ERR_STATE;
-            if (ok == 0) { cache.erase(j); continue; }         // on an earlier alignment: gone for good
-            const s64 dg = (s64)a1 - (s64)a2;
-            Cached* const hit = cache.find(j);
-            // (the selected anchors are kept in cells of NEAR_DIAG diagonals: a near one is in the anchor's
-            // cell or one next to it -- a window scans up to 64 K anchors against up to 1 K selected ones)
-            const s64 cell = (dg >= 0 ? dg : dg - (NEAR_DIAG - 1)) / NEAR_DIAG;
-            if (hit == nullptr) {
-                // 0 = not near, 1 = near (loose), 2 = near and almost on the same diagonal (tight)
-                int near = 0; u32 near_slot = 0;
-                for (s64 cc = cell - 1; cc <= cell + 1 && near < 2; cc++) {
-                    const s64 gi = cc - cell_lo;
-                    if (gi < 0 || gi >= (s64)chosen_grid.size()) continue;
-                    for (auto& c : chosen_grid[(size_t)gi])
-                        if (c.dg - dg <= NEAR_DIAG && dg - c.dg <= NEAR_DIAG &&
-                            c.a1 - (s64)a1 <= NEAR_POS && (s64)a1 - c.a1 <= NEAR_POS) {
-                            near = (c.dg - dg <= TIGHT_DIAG && dg - c.dg <= TIGHT_DIAG) ? 2 : (near < 1 ? 1 : near);
-                            near_slot = c.ext;
-                            if ((s64)a1 < c.a1) { const u32 d = (u32)(c.a1 - (s64)a1); if (d > ext_l[c.ext]) ext_l[c.ext] = d; }
-                            else                { const u32 d = (u32)((s64)a1 - c.a1); if (d > ext_r[c.ext]) ext_r[c.ext] = d; }
-                            if (near == 2) break;
-                        }
-                }
-                // a loosely near anchor is usually on the selected anchor's alignment too, but when it is not it
-                // costs a whole extra round for one DP: a bounded number of them is speculated anyway
-                if (near == 1 && insured < INSURE) { insured++; near = 0; }
-                if (near) { slot_members[near_slot].push_back({ (u32)entries.size(), a1, a2 }); entries.push_back({ j, false, near_slot }); continue; }
-            }
-            ext_of[j] = (u32)ext_l.size();
-            { const size_t gi = (size_t)(cell - cell_lo); if (chosen_grid[gi].empty()) touched.push_back((u32)gi); chosen_grid[gi].push_back({ dg, (s64)a1, (u32)ext_l.size() }); }
-            ext_l.push_back(0); ext_r.push_back(0);
-            if (slot_members.size() < ext_l.size()) slot_members.emplace_back();
-            if (prof) slot_anchor.push_back({ dg, (s64)a1 });
-            entries.push_back({ j, true, (u32)ext_l.size() - 1 });
-            if (hit != nullptr) continue;                      // result of an earlier round, re-validated at commit
-            // get_above_below, :4043-4059
-            s32 below, above;
-            above_below(S, a1, below, above);
-            // the partition holding the anchor bounds its extension, :1356-1372 / ydrop_align :2515-2531
-            u32 low1, high1, low2, high2;
-            if (!partition_limits(G.sep1, G.n_sep1, a1, G.tlen, low1, high1) || !partition_limits(G.sep2, G.n_sep2, a2, G.qlen, low2, high2)
-                || a1 + 1 > high1 || a2 + 1 > high2) return LZGPU_ERR_STATE;
-            LzDpJob L; memset(&L, 0, sizeof(L));
-            L.anchor1 = a1; L.anchor2 = a2; L.reversed = 1; L.M = a1 + 1 - low1; L.N = a2 + 1 - low2;
-            L.left_align = nb.la; L.left_seg = nb.ls; L.right_align = nb.ra; L.right_seg = nb.rs;
-            L.list_start = below;
-            LzDpJob R = L;
-            R.reversed = 0; R.M = high1 - (a1 + 1); R.N = high2 - (a2 + 1); R.list_start = above;
-            jobs.push_back(L); jobs.push_back(R);
-            Cached cr; cr.a1 = a1; cr.a2 = a2; cr.nb = nb; cr.n_snap = n_snap;
-            cache.emplace(j, std::move(cr));
-            fresh.push_back(j);
-        }
-        lap(t_window);
-        if (prof && st.rounds >= 1) { fprintf(stderr, "[lzgpu hostprof] round %u speculates anchors (rank:score):", (unsigned)st.rounds + 1); for (size_t k = 0; k < fresh.size() && k < 12; k++) fprintf(stderr, " %u:%d", fresh[k], anchors[fresh[k]].s); fprintf(stderr, " of %u entries\n", (unsigned)entries.size()); }
-        if (entries.empty()) { next = j; break; }
-        for (size_t k = 0; k < fresh.size(); k++) {            // (the extents kept growing while the window was scanned)
-            const u32 e = ext_of[fresh[k]];
-            jobs[2 * k].est_rows = ext_l[e]; jobs[2 * k + 1].est_rows = ext_r[e];
-        }
-        if (!jobs.empty()) {
-            res.assign(jobs.size(), LzDpResult());
-            ops.assign(jobs.size(), std::vector<u32>());
-            int rc = exec.run(S, jobs, res, ops);
-            if (rc) return rc;
-            for (size_t k = 0; k < fresh.size(); k++) {
-                Cached& cr = *cache.find(fresh[k]);
-                cr.rl = res[2 * k]; cr.rr = res[2 * k + 1];
-                cr.ol.swap(ops[2 * k]); cr.orr.swap(ops[2 * k + 1]);
-            }
-            for (const LzDpResult& r : res) st.dp_rows += r.max_row;
-        }
-        st.rounds++; st.dp_runs += jobs.size();
-        lap(t_exec);
-        // ---- what a commit builds from a DP pair -- the spliced script, its end trimming and rescoring, the pieces -- depends on
-        // the pair alone: done for every speculated entry of the window up front, on the helpers (splice_and_trim walks both
-        // sequences along the whole alignment: 2/3 of the serial pass it is taken out of)
-        spec_of.assign(entries.size(), 0xFFFFFFFFu);
-        spec_list.clear();
-        for (size_t e = 0; e < entries.size(); e++) if (entries[e].speculated) { spec_of[e] = (u32)spec_list.size(); spec_list.push_back((u32)e); }
-        prebuilt.clear(); prebuilt.resize(spec_list.size());
-        covered.assign(entries.size(), 0);
-        {
-            const std::function<void(size_t, size_t)> build = [&](size_t lo, size_t hi) {
-                for (size_t k = lo; k < hi; k++) {
-                    const Cached* it = cache.find(entries[spec_list[k]].anchor_ix);   // (concurrent look-ups only: nothing is inserted or erased here)
-                    if (it == nullptr) continue;
-                    const Cached& sp = *it;
-                    Prebuilt& pb = prebuilt[k];
-                    splice_and_trim(G, sp.a1, sp.a2, sp.rl, sp.ol, sp.rr, sp.orr, pb.b);
-                    format_segments(pb.b, pb.segs);
-                    pb.have = true;
-                    // ... and which of the deferred anchors found near this one lie on that alignment (a slot's members belong
-                    // to this entry alone: no two threads write the same flag); it counts once the alignment is committed
-                    const u32 slot = entries[spec_list[k]].near_slot;
-                    if (slot < slot_members.size()) for (const Member& mb : slot_members[slot]) if (on_pieces(pb.segs, mb.pos1, mb.pos2)) covered[mb.e] = 1;
-                }
-            };
-            helpers.begin_burst();
-            helpers.run(spec_list.size(), helper_min ? 16 : 1, build);
-            helpers.end_burst();
-        }
-        lap(t_prebuild);
-
-        // ---- commit in the reference's order
-        bool cut = false;
-        std::vector<s32> slot_align(ext_l.size(), -1);        // alignment committed for a selected anchor of this window
-        for (size_t e = 0; e < entries.size(); e++) {
-            const u32 aix = entries[e].anchor_ix;
-            Neighbours nb;
-            // A deferred anchor nearly always lies on the alignment of the selected anchor it was found near, and "on an
-            // alignment" needs no more than one witness (:3953-4028): that was tested for all of a slot's deferred
-            // anchors at once when the slot's alignment was committed (below); one flag to read here.  (A deferred
-            // anchor has no cached DP: nothing to erase.)
-            if (covered[e] && !entries[e].speculated && entries[e].near_slot < slot_align.size() && slot_align[entries[e].near_slot] >= 0) continue;
-            const double tq0 = prof ? now() : 0;
-            int ok = msp_left_right(S, anchors[aix].pos1, anchors[aix].pos2, nb);
-            if (prof) t_c_lr += now() - tq0;
-            if (ok < 0) return LZGPU_ERR_STATE;
-            if (ok == 0) { cache.erase(aix); continue; }       // lies on an alignment committed meanwhile
-            if (!entries[e].speculated) {                       // needs a DP: head of the next window
-                // (On the bench pair every strand has one or two of these: an anchor a few diagonals beside the long
-                // alignment of the selected anchor it was found near, 8 kbp along it.  Its DP is bounded by that very
-                // alignment, so it cannot be launched before the alignment exists: the second round is inherent.  A rule
-                // that also speculated the first anchor beyond every 1.5 kbp gap in the run of deferred anchors found
-                // nothing to add here and cost 5 ms of sorting -- not kept.)
-                if (prof && entries[e].near_slot < slot_anchor.size())
-                    fprintf(stderr, "[lzgpu hostprof] window cut at anchor %u (score %d): deferred near a selected anchor %lld diagonals and %lld bases away, not on its alignment\n",
-                            aix, anchors[aix].s, (long long)((s64)anchors[aix].pos1 - (s64)anchors[aix].pos2 - slot_anchor[entries[e].near_slot].first),
-                            (long long)((s64)anchors[aix].pos1 - slot_anchor[entries[e].near_slot].second));
-                next = aix; cut = true; break;
-            }
-            const Cached& sp = *cache.find(aix);
-            const LzDpResult& rl = sp.rl; const LzDpResult& rr = sp.rr;
-            // Is the cached DP the one the reference would run now?  Rectangles the two one-sided
-            // DPs explored, +-2 cells (target rows x query columns):
-            const s64 lr0 = (s64)sp.a1 + 1 - (s64)rl.max_row - 2, lr1 = (s64)sp.a1 + 2;
-            const s64 lc0 = (s64)sp.a2 + 1 - (s64)rl.max_col - 2, lc1 = (s64)sp.a2 + 1 - (s64)rl.min_col + 2;
-            const s64 rr0 = (s64)sp.a1 - 2, rr1 = (s64)sp.a1 + (s64)rr.max_row + 2;
-            const s64 rc0 = (s64)sp.a2 + (s64)rr.min_col - 2, rc1 = (s64)sp.a2 + (s64)rr.max_col + 2;
-            // (only alignments that overlap the two rectangles' rows can touch them: obi is ordered by pos1 and obi_maxend is
-            // the running maximum of end1, so they are a stretch of obi found by bisection -- walking every alignment
-            // committed since the snapshot was quadratic, 10 ms per strand at the north star's size)
-            const Rect2 rects = { lr0, lr1, lc0, lc1, rr0, rr1, rc0, rc1 };
-            auto touched_from = [&](size_t k0) { return touched_since(S, k0, rects); };
-            // (a) same neighbour segments at the anchor as when it ran and nothing committed since
-            //     touches what it explored: identical inputs wherever the DP looked;
-            // (b) or no alignment at all touches what it explored: every bound (L, R, masks) the
-            //     reference would track lies outside the band on every row, whichever neighbours it
-            //     starts from, so the DP is the unconstrained one.
-            bool same = nb.la == sp.nb.la && nb.ls == sp.nb.ls && nb.ra == sp.nb.ra && nb.rs == sp.nb.rs;
-            const double tq1 = prof ? now() : 0;
-            if (same) same = !touched_from(sp.n_snap);
-            else      same = !touched_from(0);
-            if (prof) t_c_chk += now() - tq1;
-            const double tq2 = prof ? now() : 0;
-            struct Lap { double& acc; double t0; bool on; std::function<double()> clk; ~Lap() { if (on) acc += clk() - t0; } } lap_build{ t_c_build, tq2, prof, now };
-            if (!same) { cache.erase(aix); next = aix; cut = true; st.reruns++; break; }
-            st.anchors_extended++;
-            st.dp_cells += rl.cells + rr.cells;
-            st.truncated += (rl.truncated ? 1 : 0) + (rr.truncated ? 1 : 0);     // :3640-3661: the reference warns on stderr
-            Prebuilt& pb = prebuilt[spec_of[e]];
-            if (!pb.have) {
-                splice_and_trim(G, sp.a1, sp.a2, rl, sp.ol, rr, sp.orr, pb.b); format_segments(pb.b, pb.segs);
-                if (entries[e].near_slot < slot_members.size()) for (const Member& mb : slot_members[entries[e].near_slot]) if (on_pieces(pb.segs, mb.pos1, mb.pos2)) covered[mb.e] = 1;
-            }
-            Built& b = pb.b;
-            std::vector<LzDpSeg>& segs = pb.segs;
-            cache.erase(aix);
-            if (segs.empty()) continue;                        // empty alignment, :1401-1405
-            if (!G.all_bounds && b.s < G.score_thresh) continue;     // :1419-1429
-            LzDpAlign m; memset(&m, 0, sizeof(m));
-            m.pos1 = b.start1; m.pos2 = b.start2; m.end1 = b.stop1; m.end2 = b.stop2;
-            m.first_seg = (s32)S.segs.size(); m.last_seg = m.first_seg + (s32)segs.size() - 1;
-            const double tq3 = prof ? now() : 0;
-            align_left_right(S, m);
-            if (prof) t_c_alr += now() - tq3;
-            S.segs.insert(S.segs.end(), segs.begin(), segs.end());
-            S.aligns.push_back(m);
-            Info in; in.s = b.s; in.beg1 = b.start1 + 1; in.beg2 = b.start2 + 1; in.end1 = b.stop1 + 1; in.end2 = b.stop2 + 1;
-            in.script.swap(b.script);
-            info.push_back(std::move(in));
-            insert_align(S, (s32)S.aligns.size() - 1);
-            const double tq4 = prof ? now() : 0;
-            if (prof) t_c_ins += tq4 - tq3;
-            struct LapC { double& acc; double t0; bool on; std::function<double()> clk; ~LapC() { if (on) acc += clk() - t0; } } lap_cov{ t_c_cov, tq4, prof, now };
-            if (entries[e].near_slot < slot_align.size()) {
-                const u32 slot = entries[e].near_slot;
-                slot_align[slot] = (s32)S.aligns.size() - 1;
-            }
-            if (G.max_paired_bases) {                          // count_paired_bases, :5695-5706; the limit test of :1441-1459
-                for (const LzDpSeg& g : segs) if (g.type == LZ_DIAG_SEG) paired_bases += (u64)g.e1 + 1 - g.b1;
-                if (paired_bases > G.max_paired_bases) return LZGPU_NH_PAIRED_LIMIT;
-            }
-        }
-        if (cut) for (size_t e = 0; e < entries.size(); e++)    // for the scan of the next window
-            if (!entries[e].speculated && entries[e].near_slot < slot_align.size()) near_align[entries[e].anchor_ix] = slot_align[entries[e].near_slot];
-        if (!cut) next = j;
-        lap(t_commit);
-    }
-    if (prof) fprintf(stderr, "[lzgpu hostprof] gapped: sort %.2f ms, windows %.2f ms, DP launches %.2f ms, pre-build %.2f ms, commit %.2f ms (neighbours %.2f, validity %.2f, build %.2f: of which neighbours of the new alignment + lists %.2f [align_left_right %.2f], coverage of deferred anchors %.2f) (%u rounds)\n",
-                      t_sort, t_window, t_exec, t_prebuild, t_commit, t_c_lr, t_c_chk, t_c_build, t_c_ins, t_c_alr, t_c_cov, (unsigned)st.rounds);
-
-    // ---- inhibitTrivial's test by sequence name (:1485-1545) cannot be made here: a result that holds a candidate for it
-    // (one diagonal piece covering a whole partition pair of equal length, base for base the same) goes back undone
-    if (delayed_check)
-        for (s32 ai : S.obi) {
-            const LzDpAlign& al = S.aligns[ai];
-            if (info[ai].s < G.score_thresh || al.first_seg != al.last_seg || S.segs[al.first_seg].type != LZ_DIAG_SEG) continue;
-            u32 lo1, hi1, lo2, hi2;
-            if (!partition_limits(G.sep1, G.n_sep1, al.pos1, G.tlen, lo1, hi1) || !partition_limits(G.sep2, G.n_sep2, al.pos2, G.qlen, lo2, hi2)) continue;
-            if (hi1 - lo1 != hi2 - lo2 || al.end1 + 1 - al.pos1 != hi1 - lo1) continue;
-            if (memcmp(G.t + al.pos1, G.q + al.pos2, al.end1 + 1 - al.pos1) == 0) return LZGPU_NH_IDENTICAL;
-        }
-    // ---- output in increasing start order (orderBegInc), :1475-1566
-    for (s32 ai : S.obi) {
-        const Info& in = info[ai];
-        if (in.s < G.score_thresh) continue;
-        if (G.inhibit_trivial && in.trivial) continue;            // :1483
-        lz_align a; a.beg1 = in.beg1; a.beg2 = in.beg2; a.end1 = in.end1; a.end2 = in.end2; a.s = in.s;
-        a.script_len = (u32)in.script.size(); a.script_off = (u32)out_ops.size();
-        out_ops.insert(out_ops.end(), in.script.begin(), in.script.end());
-        out.push_back(a);
-    }
+    p.prof.print(st.rounds);
+    if (delayed_check && p.holds_trivial_candidate()) return LZGPU_NH_IDENTICAL;    // goes back undone
+    p.emit(out, out_ops);
     return 0;
 }
 

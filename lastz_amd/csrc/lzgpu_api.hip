@@ -20,8 +20,6 @@
 // ------------------------------------------------------------------------------ context
 
 static LzCtx g_ctx;
-void lz_dp_release_statics();                                  // dp_kernels.hip
-void lz_win_release_statics();                                // window_kernels.hip
 void lz_phase_clocks_print();                                 // seed_kernels.hip (prints only in a -DLZ_PHASE_CLOCKS build)
 LzCtx& lz_ctx() { return g_ctx; }
 
@@ -208,7 +206,6 @@ extern "C" void lzgpu_shutdown(void)
     if (c.dp_stream) (void)hipStreamSynchronize(c.dp_stream);
     c.timer.resolve(); c.dp_timer.resolve();
     c.release_device_memory();                                  // (lz_ctx.hpp, beneath the members)
-    lz_dp_release_statics(); lz_win_release_statics();
     (void)hipStreamDestroy(c.stream);
     if (c.dp_stream) (void)hipStreamDestroy(c.dp_stream);
     c.stream = nullptr; c.dp_stream = nullptr; c.inited = false; c.device = -1;

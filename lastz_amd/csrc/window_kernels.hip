@@ -185,9 +185,6 @@ k_window_search(LzExtendParams P, LzSeedDev sd, const LzWinJob* __restrict__ win
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-static DevBuf g_win_jobs, g_win_scratch, g_win_out, g_win_count;
-void lz_win_release_statics() { g_win_jobs.release(); g_win_scratch.release(); g_win_out.release(); g_win_count.release(); }
-
 // the windows' HSPs in the reference's reporting order per window; counts[k] = HSPs of window k
 int lzk_window_search(LzCtx& c, const LzExtendParams& P, const LzSeedDev& sd, const lz_window* wins, u32 n, const s32* score_tab_dev,
                       std::vector<lz_hsp>& out, std::vector<u32>& counts)
@@ -199,29 +196,28 @@ int lzk_window_search(LzCtx& c, const LzExtendParams& P, const LzSeedDev& sd, co
     const u32 grid = std::min<u32>(n, (u32)cus);
     std::vector<LzWinJob> jobs(n);
     for (u32 k = 0; k < n; k++) { jobs[k].t_off = wins[k].t_off; jobs[k].t_len = wins[k].t_len; jobs[k].q_off = wins[k].q_off; jobs[k].q_len = wins[k].q_len; }
-    if ((rc = g_win_jobs.ensure((size_t)n * sizeof(LzWinJob)))) return rc;
-    if ((rc = g_win_scratch.ensure((size_t)grid * (LZ_WIN_WORDS + 1) * 2))) return rc;
-    if ((rc = g_win_count.ensure(4))) return rc;
-    LZ_HIP(hipMemcpyAsync(g_win_jobs.p, jobs.data(), (size_t)n * sizeof(LzWinJob), hipMemcpyHostToDevice, c.stream));
-    static bool attr_set = false;
-    if (!attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_window_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzWinShared))); attr_set = true; }
+    if ((rc = c.win_jobs.ensure((size_t)n * sizeof(LzWinJob)))) return rc;
+    if ((rc = c.win_scratch.ensure((size_t)grid * (LZ_WIN_WORDS + 1) * 2))) return rc;
+    if ((rc = c.win_count.ensure(4))) return rc;
+    LZ_HIP(hipMemcpyAsync(c.win_jobs.p, jobs.data(), (size_t)n * sizeof(LzWinJob), hipMemcpyHostToDevice, c.stream));
+    if (!c.win_attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_window_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzWinShared))); c.win_attr_set = true; }
     u32 cap = std::max<u32>(64u * n, 4096u);
     for (;;) {
-        if ((rc = g_win_out.ensure((size_t)cap * sizeof(LzWinHsp)))) return rc;
-        LZ_HIP(hipMemsetAsync(g_win_count.p, 0, 4, c.stream));
+        if ((rc = c.win_out.ensure((size_t)cap * sizeof(LzWinHsp)))) return rc;
+        LZ_HIP(hipMemsetAsync(c.win_count.p, 0, 4, c.stream));
         c.timer.begin("k_window_search", c.stream);
         hipLaunchKernelGGL(k_window_search, dim3(grid), dim3(LZ_WIN_TPB), sizeof(LzWinShared), c.stream,
-                           P, sd, g_win_jobs.as<LzWinJob>(), n, score_tab_dev, g_win_scratch.as<unsigned short>(),
-                           g_win_out.as<LzWinHsp>(), g_win_count.as<u32>(), cap);
+                           P, sd, c.win_jobs.as<LzWinJob>(), n, score_tab_dev, c.win_scratch.as<unsigned short>(),
+                           c.win_out.as<LzWinHsp>(), c.win_count.as<u32>(), cap);
         c.timer.end(c.stream);
         LZ_HIP(hipGetLastError());
         u32 got = 0;
-        LZ_HIP(hipMemcpyAsync(&got, g_win_count.p, 4, hipMemcpyDeviceToHost, c.stream));
+        LZ_HIP(hipMemcpyAsync(&got, c.win_count.p, 4, hipMemcpyDeviceToHost, c.stream));
         LZ_HIP(hipStreamSynchronize(c.stream));
         c.timer.resolve();
         if (got <= cap) {
             std::vector<LzWinHsp> recs(got);
-            if (got) LZ_HIP(hipMemcpy(recs.data(), g_win_out.p, (size_t)got * sizeof(LzWinHsp), hipMemcpyDeviceToHost));
+            if (got) LZ_HIP(hipMemcpy(recs.data(), c.win_out.p, (size_t)got * sizeof(LzWinHsp), hipMemcpyDeviceToHost));
             // reporting order inside a window: query position up, target position down (:506-512, :832)
             std::sort(recs.begin(), recs.end(), [](const LzWinHsp& x, const LzWinHsp& y) {
                 if (x.win != y.win) return x.win < y.win;

@@ -331,3 +331,58 @@ def test_dp_codes_follow_the_bytes_of_a_resident_slot(gpu):
             assert same(via_slot, via_host)
             n_checked += len(via_slot[0])
     assert n_checked > 20
+
+
+def test_same_alignments_after_shutdown_and_init(gpu):
+    """The gapped twin of test_gpu_seed.py::test_same_results_after_shutdown_and_init.  The obstacle-course slice of
+    `adversarial` (hundreds of alignments bounding and masking each other, more than three rounds: the piece arena, both id
+    lists and the ops gather are all in use) through the search and gapped_extend with 64 KiB slots, so that the retry path
+    allocates too, then one window_search over a handful of windows of the same pair; shutdown + init; the same again.
+    Alignments, edit ops, window HSPs and the gapped counters equal the first pass and the oracle's gapped_extend.  The
+    set_dp_window / set_dp_slot values are set once, before the first pass: the second pass runs under them only if they
+    outlive the shutdown (its counters and launch count then equal the first pass's and differ from a run under the defaults).
+    A guard on results: that shutdown releases every buffer of the stage is read off LzCtx::release_device_memory against the
+    member list (lz_ctx.hpp), not shown here -- on one device a stale pointer would still work."""
+    sub, masked = H.scoring()
+    t, q = H.load_case("adversarial")
+    t, q = t[9000:14500], q[29500:34000]
+    wins = [(0, 2000, 0, 2000), (1500, 3000, 1000, 3500), (3000, 2500, 2000, 2500), (100, 5000, 50, 4000), (5000, 500, 4000, 500)]
+    isd = gpu.seed("1111111", 0)
+
+    def one_pass():
+        gpu.table_prepare(t, gpu.seed(), CTB)
+        hsps = gpu.seed_hit_search(masked, q=q)
+        segs = np.zeros(len(hsps), dtype=lzgpu.SEG_DTYPE)
+        segs["pos1"] = hsps["pos1"] - hsps["length"]; segs["pos2"] = hsps["pos2"] - hsps["length"]
+        segs["length"] = hsps["length"]; segs["s"] = hsps["score"]
+        gpu.counters_reset(); gpu.profile_reset(); gpu.profile_enable(True)
+        al, ops = gpu.gapped_extend(sub, segs, q=q)
+        c = gpu.counters()
+        launches = gpu.profile().get("k_ydrop", {"launches": 0})["launches"]
+        gpu.profile_enable(False)
+        found = gpu.window_search(masked, wins, isd, CTB, q=q, hsp_threshold=2200)
+        gapped = {k: c[k] for k in ("anchors_extended", "dp_cells", "gapped_extensions", "truncated_extensions", "dp_rows")}
+        return al, ops, found, gapped, launches
+
+    ohsps, _ = lzo.seed_hit_search(lzo.Table(t, lzo.seed()), q, masked)
+    osegs = lzo.hsps_to_segments(ohsps, 0)
+    oal, oops, ost = lzo.gapped_extend(t, q, sub, lzo.reduce_to_points(t, q, sub, osegs))
+    try:
+        gpu.set_dp_window(2); gpu.set_dp_slot(65536)
+        al0, ops0, found0, c0, n0 = one_pass()
+        gpu.shutdown(); gpu.init()
+        al1, ops1, found1, c1, n1 = one_pass()
+    finally:
+        gpu.set_dp_window(0); gpu.set_dp_slot(8 << 20)
+    assert len(oal) > 100 and len(al0) == len(oal) and (al0 == oal).all() and (ops0 == oops).all()
+    assert c0["dp_cells"] == ost["dp_cells"] and c0["anchors_extended"] == ost["anchors_extended"]
+    assert len(al1) == len(al0) and (al1 == al0).all() and len(ops1) == len(ops0) and (ops1 == ops0).all()
+    assert sum(len(f) for f in found0) > 0 and len(found1) == len(found0)
+    assert all(len(x) == len(y) and (x == y).all() for x, y in zip(found0, found1))
+    # every round launches at least one anchor's two DPs, so without retries a call has at most gapped_extensions / 2 launches:
+    # more than that in the first pass means the 64 KiB slots did send DPs through the retry path
+    assert n0 > c0["gapped_extensions"] // 2
+    assert c1 == c0 and n1 == n0
+    al2, ops2, _, c2, n2 = one_pass()                            # under the defaults: fewer launches (no retries), other rounds
+    assert (al2 == oal).all() and (ops2 == oops).all()
+    assert c2["gapped_extensions"] != c0["gapped_extensions"] and n2 < n0
