@@ -94,7 +94,8 @@ struct HipDpExec : LzDpExecutor {
     LzCtx::DpBufs& d;                    // (touched only by the thread that holds the rendezvous, on c.dp_stream)
     LzDpParams P;                        // arenas filled per launch
     u32 slot_tb;                         // first-try traceback slot (bytes) per DP
-    explicit HipDpExec(LzCtx& ctx) : c(ctx), d(ctx.dp) {}
+    const LzDpSwitches sw;               // the call's (lz_settings.hpp)
+    HipDpExec(LzCtx& ctx, const LzDpSwitches& s) : c(ctx), d(ctx.dp), sw(s) {}
 
     u64 wide_runs = 0;
     double t_upload = 0, t_kernel = 0, t_ops = 0;               // LZGPU_HOSTPROF: host milliseconds in launch() / fetch_ops()
@@ -191,13 +192,10 @@ struct HipDpExec : LzDpExecutor {
     int launch_ring(size_t n_free, size_t n_bound)
     {
         const u64 n = n_free + n_bound;
-        const char* const narrow_env = getenv("LZGPU_DP_NARROW");
-        const bool narrow = row16_ok && (narrow_env ? narrow_env[0] == '1' : n > 2u * (u64)LZ_DP_WPE_FREE * (u64)c.num_cus);
+        const bool narrow = row16_ok && (sw.narrow >= 0 ? sw.narrow == 1 : n > 2u * (u64)LZ_DP_WPE_FREE * (u64)c.num_cus);
         if (narrow) jobs_narrow += n;
         c.dp_timer.begin(narrow ? "k_ydrop_n" : "k_ydrop", c.dp_stream);
-        static const size_t pad_lds = []() { const char* e = getenv("LZGPU_DP_PAD_LDS"); return (size_t)(e ? atol(e) : 0); }();   // occupancy experiments: fewer DPs per CU
-        const size_t dyn_lds = (size_t)tab_rows * LZ_NCLASS * sizeof(s32) + pad_lds;
-        const char* const repl_env = getenv("LZGPU_DP_REPL");                             // tests / A-B: force one form of the row set-up
+        const size_t dyn_lds = (size_t)tab_rows * LZ_NCLASS * sizeof(s32);
         using Kern = void (*)(const LzDpProblem*, LzDpParams, const LzDpJob*, const u32*, const s32*, LzDpResult*, u32);
         static const Kern kerns[2][2][2] = {                                              // [no_trim][bounds][repl]
             { { k_ydrop<false, false, false>, k_ydrop<false, false, true> }, { k_ydrop<false, true, false>, k_ydrop<false, true, true> } },
@@ -209,7 +207,7 @@ struct HipDpExec : LzDpExecutor {
             if (!cnt) return 0;
             const u64 per_cu = narrow ? lzk_ydrop_narrow_per_cu(bounds) : (u64)(bounds ? LZ_DP_WPE : LZ_DP_WPE_FREE);
             bool repl = n <= 2u * per_cu * (u64)c.num_cus;
-            if (repl_env) repl = repl_env[0] == '1';
+            if (sw.repl >= 0) repl = sw.repl == 1;                                        // tests / A-B: force one form of the row set-up
             const u32* idp = d.ids.as<u32>() + first;
             if (narrow) return lzk_ydrop_narrow(P.no_trim != 0, bounds, repl, (unsigned)cnt, dyn_lds, c.dp_stream, problems_dev, P, d.jobs.as<LzDpJob>(), idp, d.tab.as<s32>(), d.res.as<LzDpResult>(), tab_rows);
             hipLaunchKernelGGL(kerns[P.no_trim != 0][bounds][repl], dim3((unsigned)cnt), dim3(LZ_DP_LANES), dyn_lds, c.dp_stream, problems_dev, P, d.jobs.as<LzDpJob>(), idp, d.tab.as<s32>(), d.res.as<LzDpResult>(), tab_rows);
@@ -233,9 +231,9 @@ struct HipDpExec : LzDpExecutor {
     }
 
     // profiling aids -- LZGPU_DPDUMP=<file>: one line per DP of the launch; LZGPU_DPPROF: the longest DP of the launch, by step
-    static void report(const char* dump, bool dpprof, const std::vector<LzDpJob>& jobs, const std::vector<u32>& ids, const std::vector<LzDpResult>& all, u32 slot)
+    static void report(const std::string& dump, bool dpprof, const std::vector<LzDpJob>& jobs, const std::vector<u32>& ids, const std::vector<LzDpResult>& all, u32 slot)
     {
-        if (dump) if (FILE* f = fopen(dump, "a")) {
+        if (!dump.empty()) if (FILE* f = fopen(dump.c_str(), "a")) {
             for (u32 id : ids) fprintf(f, "%u %u %llu %u %u %llu %llu %llu\n", jobs[id].est_rows, all[id].max_row, (unsigned long long)all[id].cells, all[id].status, slot,
                                        (unsigned long long)all[id].t_rows, (unsigned long long)all[id].t_begin, (unsigned long long)all[id].t_end);
             fclose(f);
@@ -280,8 +278,7 @@ struct HipDpExec : LzDpExecutor {
         std::vector<LzDpResult> all(jobs.size());
         if ((rc = read_results(ids, all, res))) return rc;
         t_kernel += ms_since(lt1);
-        const char* const dump = getenv("LZGPU_DPDUMP"); const bool dpprof = getenv("LZGPU_DPPROF") != nullptr;
-        if (dump || dpprof) report(dump, dpprof, jobs, ids, all, slot);
+        if (!sw.dump.empty() || sw.prof) report(sw.dump, sw.prof, jobs, ids, all, slot);
         return 0;
     }
 
@@ -357,7 +354,7 @@ struct HipDpExec : LzDpExecutor {
         // rows a job's pieces are worked out for at first: well past what its DP is expected to sweep (est_rows: the host's guess from
         // the deferred anchors around it; rows = 1.2 x est_rows at the median, 2.2 x at the 90th percentile), never past its last row
         horizon.resize(jobs.size());
-        static const u32 first_h = []() { const char* e = getenv("LZGPU_DP_HORIZON"); return (u32)(e ? atoi(e) : 0); }();       // tests: a short one
+        const u32 first_h = lz_settings().dp_horizon;          // tests: a short one
         for (size_t k = 0; k < jobs.size(); k++) horizon[k] = std::min<u32>(jobs[k].M, first_h ? first_h : std::max<u32>(4u * jobs[k].est_rows + 4096u, 16384u));
         LZ_HIP(hipMemcpyAsync(d.problems.p, pb.data(), pb.size() * sizeof(LzDpProblem), hipMemcpyHostToDevice, c.dp_stream));
         problems_dev = d.problems.as<LzDpProblem>();
@@ -369,13 +366,11 @@ struct HipDpExec : LzDpExecutor {
         for (u32 k = 0; k < jobs.size(); k++) ids[k] = k;
         // blocks are dispatched in index order and a CU holds four DPs: the DPs expected to sweep the most rows go
         // first (est_rows, lz_gapped_host.cpp), so that the launch does not end on a long DP that started late
-        if (!getenv("LZGPU_DP_NO_ORDER"))
-            std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return jobs[a].est_rows > jobs[b].est_rows; });
-        static const bool uniform_slots = getenv("LZGPU_DP_UNIFORM_SLOTS") != nullptr;     // A/B aid: round 2's arena
+        std::stable_sort(ids.begin(), ids.end(), [&](u32 a, u32 b) { return jobs[a].est_rows > jobs[b].est_rows; });
         u32 slot = slot_tb;
         // (a launch of a few DPs -- the later rounds of a strand -- takes uniform slots at once: a DP that overflows its
         // estimated slot costs a launch of its own, 2.8 ms for six DPs on the bench pair, and 256 uniform slots are 2 GiB)
-        bool first_try = !uniform_slots && jobs.size() > 256;
+        bool first_try = jobs.size() > 256;
         while (!ids.empty() || !wide_ids.empty()) {
             u64 max_jobs = DP_ARENA_BUDGET / DpSlot{ slot }.bytes(); if (max_jobs < 1) max_jobs = 1;
             std::vector<u32> retry, retry_wide, again, again_wide;       // in a larger slot / with pieces up to a farther horizon
@@ -489,7 +484,7 @@ int ensure_dp_codes(LzCtx& c, SeqSlot& s, const u8 cls[256], u32 len)
 }
 
 // query slot + window + DP class codes of one problem; `temp_slot` names the slot a host pointer is uploaded to
-int gapped_prepare(LzCtx& c, const lz_gapped_args* a, int temp_slot, const u8 rowc[256], const u8 colc[256], bool encode_target,
+int gapped_prepare(LzCtx& c, const lz_gapped_args* a, u32 window_env, int temp_slot, const u8 rowc[256], const u8 colc[256], bool encode_target,
                    std::map<SeqSlot*, bool>& encoded, GappedProblem& gp)
 {
     int rc;
@@ -516,12 +511,11 @@ int gapped_prepare(LzCtx& c, const lz_gapped_args* a, int temp_slot, const u8 ro
     LzGappedParams& G = gp.G;
     G.t = c.target.host.data() + a->t_off; G.tlen = gp.tlen; G.q = qhost + a->q_off; G.qlen = gp.qlen; G.sub = a->sub;
     G.gap_open = a->gap_open; G.gap_extend = a->gap_extend; G.ydrop = a->ydrop; G.score_thresh = a->score_thresh;
-    G.window = c.dp_window ? c.dp_window : std::min<u32>(16384u, std::max<u32>(2048u, a->n_anchors / 32u));
+    G.window = window_env ? window_env : c.dp_window ? c.dp_window : std::min<u32>(16384u, std::max<u32>(2048u, a->n_anchors / 32u));
     G.sep1 = a->sep1; G.n_sep1 = a->sep1 ? a->n_sep1 : 0; G.sep2 = a->sep2; G.n_sep2 = a->sep2 ? a->n_sep2 : 0;
     G.strands_differ = a->strands_differ != 0; G.inhibit_trivial = a->inhibit_trivial != 0;
     G.all_bounds = a->all_bounds != 0; G.max_paired_bases = a->max_paired_bases;
     if ((a->sep1 && a->n_sep1 < 2) || (a->sep2 && a->n_sep2 < 2)) return lz_fail(LZGPU_ERR_ARG, "a partitioned sequence needs at least two separators");
-    if (const char* w = getenv("LZGPU_DP_WINDOW")) { const int v = atoi(w); if (v > 0) G.window = (u32)v; }
     return 0;
 }
 int gapped_result(std::vector<lz_align>& al, std::vector<u32>& op, lz_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops)
@@ -539,6 +533,7 @@ int gapped_result(std::vector<lz_align>& al, std::vector<u32>& op, lz_align** ou
 extern "C" int lzgpu_gapped_extend_batch(const lz_gapped_args* args, uint32_t n, lz_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops)
 {
     LzCtx& c = lz_ctx();
+    const LzDpSwitches sw = lz_dp_switches();                  // (once per call, before any worker thread: lz_settings.hpp)
     if (!args || !out || !n_out || !ops || !n_ops || n == 0) return lz_fail(LZGPU_ERR_ARG, "null argument");
     for (u32 k = 0; k < n; k++) { out[k] = nullptr; n_out[k] = 0; ops[k] = nullptr; n_ops[k] = 0; }
     { int rc0 = lz_bind_thread(); if (rc0) return rc0; }
@@ -555,7 +550,7 @@ extern "C" int lzgpu_gapped_extend_batch(const lz_gapped_args* args, uint32_t n,
     }
     if (a0.gap_extend <= 0) return LZGPU_NH_UNSUPPORTED;
     int rc;
-    static const bool hprof = getenv("LZGPU_HOSTPROF") != nullptr;
+    const bool hprof = lz_settings().hostprof;
     const auto hp0 = std::chrono::steady_clock::now();
     auto hp_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - hp0).count(); };
     u8 rowc[256], colc[256]; s32 tab[LZ_NCLASS * LZ_NCLASS];
@@ -563,12 +558,12 @@ extern "C" int lzgpu_gapped_extend_batch(const lz_gapped_args* args, uint32_t n,
     std::vector<GappedProblem> gp(n);
     std::map<SeqSlot*, bool> encoded;                          // (problems may share a query slot -- the windows of a strand: encoded once)
     for (u32 k = 0; k < n; k++)
-        if ((rc = gapped_prepare(c, &args[k], LZ_TEMP_SLOT_B3 - (int)k, rowc, colc, k == 0, encoded, gp[k]))) return rc;    // (B2's transient slot is -1: the two ranges are disjoint)
+        if ((rc = gapped_prepare(c, &args[k], sw.window, LZ_TEMP_SLOT_B3 - (int)k, rowc, colc, k == 0, encoded, gp[k]))) return rc;    // (B2's transient slot is -1: the two ranges are disjoint)
     if ((rc = c.dp.tab.ensure(sizeof(tab)))) return rc;
     LZ_HIP(hipMemcpyAsync(c.dp.tab.p, tab, sizeof(tab), hipMemcpyHostToDevice, c.dp_stream));
     LZ_HIP(hipStreamSynchronize(c.dp_stream));
 
-    HipDpExec ex(c);
+    HipDpExec ex(c, sw);
     ex.P.tdp = gp[0].tdp; ex.P.tlen = gp[0].tlen; ex.P.qdp = gp[0].qdp; ex.P.qlen = gp[0].qlen;
     ex.P.gap_e = a0.gap_extend; ex.P.gap_oe = a0.gap_open + a0.gap_extend; ex.P.ydrop = a0.ydrop;
     ex.P.ydrop_tail = a0.ydrop / a0.gap_extend + 6;                      // :3484-3492
@@ -584,8 +579,7 @@ extern "C" int lzgpu_gapped_extend_batch(const lz_gapped_args* args, uint32_t n,
     // rendezvous and takes the next one when it is done, so `active` -- the number of submissions a launch waits
     // for -- is the number of workers that still have a problem in hand.
     const double hp_prepared = hp_ms();
-    static const u32 pool_cap = []() { const char* e = getenv("LZGPU_BATCH_THREADS"); const int v = e ? atoi(e) : 0; return (u32)(v > 0 ? v : 64); }();
-    const u32 want = std::min<u32>(n, pool_cap);
+    const u32 want = std::min<u32>(n, lz_settings().batch_threads);
     DpRendezvous R(ex, 0);
     std::vector<std::vector<lz_align>> al(n); std::vector<std::vector<u32>> op(n); std::vector<LzGappedStats> st(n); std::vector<int> rcs(n, 0);
     const int dev = c.device;

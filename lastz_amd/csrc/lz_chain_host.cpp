@@ -27,6 +27,7 @@
 #include <atomic>
 #include <system_error>
 #include "lz_common.hpp"
+#include "lz_settings.hpp"
 #include "../../include/lzgpu.h"
 
 int lz_fail(int code, const char* fmt, ...);
@@ -214,7 +215,7 @@ extern "C" int lzgpu_reduce_to_chain_batch(const lz_chain_args* a, const lz_segm
 {
     if (!a || !segs || !n || !kept || !n_kept || k == 0) return lz_fail(LZGPU_ERR_ARG, "lzgpu_reduce_to_chain_batch: null argument");
     for (u32 j = 0; j < k; j++) { kept[j] = nullptr; n_kept[j] = 0; if (best) best[j] = 0; }
-    static const u32 cap = []() { const char* e = getenv("LZGPU_CHAIN_THREADS"); const int v = e ? atoi(e) : 0; return (u32)(v > 0 ? v : 16); }();
+    const u32 cap = lz_settings().chain_threads;
     std::vector<int> rcs(k, 0);
     std::atomic<u32> next{0};
     auto work = [&]() {

@@ -6,6 +6,7 @@
 #include <map>
 #include <mutex>
 #include "lz_common.hpp"
+#include "lz_settings.hpp"
 #include "../../include/lzgpu.h"
 
 struct DevBuf {                     // growable device allocation
@@ -123,7 +124,7 @@ struct LzCtx {
     // Anchors speculated per round.  A launch lasts as long as its longest DP, so the fewer rounds the better: 2048 holds
     // the ~1150 anchors of a 50 Mbp strand that need a DP in one launch; a 200 Mbp strand has ~4500 (north star:
     // 7 launches, 0.73 s at 2048; 5 launches, 0.48 s at 8192 and beyond).  Default: 1/32 of the anchors, within [2048, 16384].
-    u32 dp_window = 0;                // 0: the default rule; lzgpu_set_dp_window / LZGPU_DP_WINDOW fix it
+    u32 dp_window = 0;                // 0: the default rule; lzgpu_set_dp_window fixes it (LZGPU_DP_WINDOW, for one call, goes before either)
     u32 n_owners = 1, owner = 0;      // bucket ownership (lzgpu_set_bucket_owner)
     LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self); mode LZ_SELF_OFF otherwise
     DevBuf self_sep;                  // its separators on the device: sep1, then sep2

@@ -11,6 +11,7 @@
 #include <deque>
 #include "lz_gapped_host.hpp"
 #include "lz_host.hpp"
+#include "lz_settings.hpp"
 
 #include <atomic>
 #include <mutex>
@@ -415,8 +416,7 @@ struct GappedProf {
     double c_lr = 0, c_chk = 0, c_build = 0, c_ins = 0, c_alr = 0, c_cov = 0;         // inside commit (c_build holds c_ins and c_cov, c_ins holds c_alr)
     double mark;
     static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    static bool enabled() { static const bool e = getenv("LZGPU_HOSTPROF") != nullptr; return e; }
-    GappedProf() : on(enabled()), mark(on ? now() : 0) {}
+    GappedProf() : on(lz_settings().hostprof), mark(on ? now() : 0) {}
     void lap(double& acc) { if (!on) return; const double t = now(); acc += t - mark; mark = t; }
     struct Scope {
         double* const acc; const double t0;
@@ -493,14 +493,13 @@ struct GappedWindow {
     }
 };
 
-static u32 helper_min_anchors() { static const u32 v = []() { const char* e = getenv("LZGPU_HELPER_MIN_ANCHORS"); return (u32)(e ? atoi(e) : 20000); }(); return v; }   // (tests: 0)
 // (three helpers for a 50 Mbp strand's 79 k anchors; seven from 150 k anchors on -- a 200 Mbp strand has 300 k, 9 k alignments to build per round:
 // gapped stage 0.230-0.245 -> 0.222-0.231 s; LZGPU_HELPERS fixes the number)
 static u32 helper_count(u32 n_anchors)
 {
-    static const u32 helper_env = []() { const char* e = getenv("LZGPU_HELPERS"); const int v = e ? atoi(e) : 0; return (u32)(v > 0 ? v : 0); }();
-    const u32 helper_n = helper_env ? helper_env : (n_anchors >= 150000u ? 7u : 3u);
-    return n_anchors >= helper_min_anchors() ? helper_n : 0u;   // (small problems -- tweener windows -- stay on their own thread)
+    const LzSettings& S = lz_settings();
+    const u32 helper_n = S.helpers ? S.helpers : (n_anchors >= 150000u ? 7u : 3u);
+    return n_anchors >= S.helper_min_anchors ? helper_n : 0u;   // (small problems -- tweener windows -- stay on their own thread)
 }
 
 // What lives across the windows of one lzh_gapped_extend call.
@@ -717,7 +716,7 @@ struct GappedPass {
             }
         };
         helpers.begin_burst();
-        helpers.run(w.spec_list.size(), helper_min_anchors() ? 16 : 1, build);
+        helpers.run(w.spec_list.size(), lz_settings().helper_min_anchors ? 16 : 1, build);
         helpers.end_burst();
         prof.lap(prof.prebuild);
     }

@@ -42,7 +42,7 @@ int lz_fail(int code, const char* fmt, ...)
 int DevBuf::ensure(size_t bytes)
 {
     if (bytes <= cap && p) return 0;
-    static const bool prof = getenv("LZGPU_HOSTPROF") != nullptr;
+    const bool prof = lz_settings().hostprof;
     const auto t0 = std::chrono::steady_clock::now();
     const size_t old = cap;
     if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -77,8 +77,8 @@ hipEvent_t KernelTimer::get_event(hipStream_t s)
 void KernelTimer::begin(const char* name, hipStream_t s)
 {
     if (!enabled) return;
-    static const char* only = getenv("LZGPU_TIMER_ONLY");        // profiling aid: time just this kernel
-    if (only && strcmp(only, name) != 0) { cur = -1; return; }
+    const std::string& only = lz_settings().timer_only;         // profiling aid: time just this kernel
+    if (!only.empty() && only != name) { cur = -1; return; }
     cur = id_of(name); cur_a = get_event(s);
     (void)hipEventRecord(cur_a, s);
 }
@@ -94,7 +94,7 @@ void KernelTimer::resolve()
 {
     // LZGPU_GAPS=1 (profiling aid): idle time on a stream between the end of one timed kernel and the
     // start of the next, reported when it exceeds 0.3 ms
-    static const bool gaps = getenv("LZGPU_GAPS") != nullptr;
+    const bool gaps = lz_settings().gaps;
     static std::map<hipStream_t, Pending> last;
     std::vector<Pending> later;
     for (auto& p : pending) {
@@ -164,8 +164,9 @@ static int lz_init_locked(int device_index)
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device_index) == hipSuccess && prop.multiProcessorCount > 0) g_ctx.num_cus = prop.multiProcessorCount; }
     LZ_HIP(hipStreamCreateWithFlags(&g_ctx.stream, hipStreamNonBlocking));
     LZ_HIP(hipStreamCreateWithFlags(&g_ctx.dp_stream, hipStreamNonBlocking));
-    if (const char* sm = getenv("LZGPU_SCAN_MODE")) { const int v = atoi(sm); if (v >= 0 && v <= 2) g_ctx.min_scan_mode = v; }
-    if (const char* hc = getenv("LZGPU_HIT_CAPACITY")) { const long long v = atoll(hc); if (v >= 1024 && v <= (1ll << 31)) g_ctx.hit_capacity = (u64)v; }
+    const LzSettings& S = lz_settings();                       // (the first init of the process reads them)
+    if (S.scan_mode >= 0) g_ctx.min_scan_mode = S.scan_mode;
+    if (S.hit_capacity) g_ctx.hit_capacity = S.hit_capacity;
     g_ctx.device = device_index;
     g_ctx.inited = true;
     return 0;
@@ -450,10 +451,10 @@ extern "C" int lzgpu_device_copy(void* dst, const void* src, uint64_t bytes)
 
 #include <chrono>
 struct HostProf {
-    bool on; double t[16]; const char* names[16] = { nullptr }; int n = 0;
+    bool on = false; double t[16]; const char* names[16] = { nullptr }; int n = 0;
     std::chrono::steady_clock::time_point last;
-    HostProf() { on = getenv("LZGPU_HOSTPROF") != nullptr; for (auto& x : t) x = 0; }
-    void start() { if (on) last = std::chrono::steady_clock::now(); }
+    HostProf() { for (auto& x : t) x = 0; }
+    void start() { on = lz_settings().hostprof; if (on) last = std::chrono::steady_clock::now(); }
     void lap(int k, const char* name) {
         if (!on) return;
         auto now = std::chrono::steady_clock::now();
@@ -679,8 +680,7 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
     // records in keys and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
     // the fill variant in use is one the fused kernel does not reproduce (bucket owners), or
     // wctx cannot be had (lz_wctx_prepare)
-    static const bool fused_off = getenv("LZGPU_FUSED_SCAN") != nullptr && atoi(getenv("LZGPU_FUSED_SCAN")) == 0;
-    s.fused = a->extend && mode == 0 && s.max_chunk && !fused_off && c.n_owners <= 1;
+    s.fused = a->extend && mode == 0 && s.max_chunk && lz_settings().fused_scan && c.n_owners <= 1;
     if (s.fused && (rc = lz_wctx_prepare(c, s.fused))) return rc;
     return 0;
 }

@@ -324,12 +324,10 @@ int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk,
     // ... and only for a search that will need several chunks (measured: with one chunk per strand the blocks buy nothing -- the fill
     // kernel's 18-or-28 ms do not come from the range of its scatter -- and cost k_count_hits 0.8 ms of shared wstart[] lines; at 200 Mbp,
     // 29 chunks per strand, the launches' ranges take the fill from 292 to 232 ms per step): twice as many blocks as expected chunks
-    static const int force_bits = []() { const char* e = getenv("LZGPU_BLOCK_BITS"); const int v = e ? atoi(e) : -1; return v > 7 ? 7 : v; }();   // A/B
     const double est_hits = (double)n * (double)c.num_words * (double)c.seed.nprobes / (double)(1ull << c.seed.weight);
     u32 want_bits = 0;
     while (want_bits < 5 && est_hits > (double)c.hit_capacity * (double)(1u << want_bits) * 0.5) want_bits++;
     if (est_hits <= (double)c.hit_capacity) want_bits = 0;
-    if (force_bits >= 0) want_bits = (u32)force_bits;
     u32 bbits = std::min<u32>(want_bits, 32u - kbits);
     u32 bshift = 0;
     const u64 nm1 = n ? (u64)n - 1 : 0;
@@ -1113,9 +1111,7 @@ k_partition(u64* recs, u64 n, u32* __restrict__ hist, u32* __restrict__ run_addr
 
 static int lz_scan_tpb(int mode)
 {
-    static const int env = getenv("LZGPU_SC_TPB") ? atoi(getenv("LZGPU_SC_TPB")) : 0;      // A/B aid: 512, 640, 768 or 1024
-    if (mode != 0) return LZ_SC_TPB;
-    return (env == 512 || env == 640 || env == 768 || env == 1024) ? env : 640;     // 640: five waves per SIMD at 89 VGPRs (512: 72.5, 640: 69.7, 768 with 8 spilled registers: 75.9 ms per step)
+    return mode != 0 ? LZ_SC_TPB : 640;     // 640: five waves per SIMD at 89 VGPRs (512: 72.5, 640: 69.7, 768 with 8 spilled registers: 75.9 ms per step)
 }
 // The task list for n hits scanned by n_regions waves (k_scan_hits in `mode`, or k_scan_hits2 as mode 0): one region
 // per wave, room for 1/32 of the wave's hits + 64; a hit that finds its region full is left to phase B.
@@ -1125,8 +1121,7 @@ static int lz_scan_tpb(int mode)
 static int lz_task_regions(LzCtx& c, int mode, u64 n, u32 n_regions, u32& region_cap)
 {
     region_cap = (u32)std::min<u64>(n / (mode == 1 ? 12 : 32) / n_regions + 64, 1u << 20);
-    static const char* force = getenv("LZGPU_TASK_REGION_CAP");  // test hook: tiny regions, so that hits find theirs full
-    if (force && atoi(force) > 0) region_cap = (u32)atoi(force);
+    if (const u32 force = lz_settings().task_region_cap) region_cap = force;   // test hook: tiny regions, so that hits find theirs full
     int rc;
     if (mode < 2 && (rc = c.scan_tasks.ensure((size_t)n_regions * region_cap * sizeof(LzScanTask)))) return rc;
     return c.scan_ntasks.ensure((size_t)n_regions * 4);
@@ -1136,9 +1131,8 @@ static int lz_scan_buffers(LzCtx& c, int mode, u64 n, u32& grid, u32& n_regions,
 {
     const u32 wpg = (u32)lz_scan_tpb(mode) / 64u;
     const int cus = c.num_cus;
-    static const u32 wgs = getenv("LZGPU_PP_WGS") ? (u32)atoi(getenv("LZGPU_PP_WGS")) : 2u;
     const u64 nspans = (n + 64u * LZ_SC_ROUNDS - 1) / (64u * LZ_SC_ROUNDS), want = (nspans + wpg - 1) / wpg;
-    grid = (u32)std::min<u64>(want ? want : 1, (u64)wgs * (u64)cus);
+    grid = (u32)std::min<u64>(want ? want : 1, 2u * (u64)cus);                 // two workgroups per CU
     n_regions = grid * wpg;
     const int rc = c.summ.ensure((size_t)n * 4);
     return rc ? rc : lz_task_regions(c, mode, n, n_regions, region_cap);
@@ -1161,14 +1155,8 @@ int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams
     if ((rc = lz_scan_buffers(c, mode, n, grid, n_regions, task_cap))) return rc;
     u32* summ = c.summ.as<u32>(); LzScanTask* tasks = c.scan_tasks.as<LzScanTask>(); u32* ntk = c.scan_ntasks.as<u32>();
     c.timer.begin("k_scan_hits", st);
-    const int tpb = lz_scan_tpb(mode);
 #define LZ_SCAN_LAUNCH(M_, T_, W_) hipLaunchKernelGGL((k_scan_hits<M_, T_, W_>), dim3(grid), dim3(T_), 0, st, P, Q, keys, n, score_tab, lut, summ, bins, tasks, ntk, task_cap)
-    if (mode == 0) {
-        if (tpb == 640)       LZ_SCAN_LAUNCH(0, 640, 5);
-        else if (tpb == 768)  LZ_SCAN_LAUNCH(0, 768, 6);
-        else if (tpb == 1024) LZ_SCAN_LAUNCH(0, 1024, 8);
-        else                  LZ_SCAN_LAUNCH(0, 512, 4);
-    }
+    if (mode == 0)      LZ_SCAN_LAUNCH(0, 640, 5);              // (lz_scan_tpb)
     else if (mode == 1) LZ_SCAN_LAUNCH(1, LZ_SC_TPB, 4);
     else                LZ_SCAN_LAUNCH(2, LZ_SC_TPB, 4);
 #undef LZ_SCAN_LAUNCH
@@ -1379,9 +1367,7 @@ int lzk_wctx_build(LzCtx& c)
 // self-comparison's clipping needs 177 registers: it runs with 8 waves.
 static u32 lz_fused_tpb(LzCtx& c)
 {
-    static const int env = getenv("LZGPU_FUSE_TPB") ? atoi(getenv("LZGPU_FUSE_TPB")) : 0;  // A/B aid: 512, 768 or 1024
-    if (c.self.mode != LZ_SELF_OFF) return 512u;
-    return (env == 512 || env == 768 || env == 1024) ? (u32)env : 1024u;
+    return c.self.mode != LZ_SELF_OFF ? 512u : 1024u;
 }
 // the fused kernel's grid (one workgroup per CU: its LDS) and the task list
 static int lz_fused_buffers(LzCtx& c, u64 n_hits, u32& grid, u32& n_regions, u32& region_cap)
@@ -1407,12 +1393,9 @@ int lzk_scan_fused(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* s
     if ((rc = lz_fused_buffers(c, n_hits, grid, n_regions, region_cap))) return rc;
     LzScanTask* tasks = c.scan_tasks.as<LzScanTask>(); u32* ntk = c.scan_ntasks.as<u32>();
     c.timer.begin("k_scan_hits", st);
-    const u32 tpb = lz_fused_tpb(c);
 #define LZ_FUSED_LAUNCH(S_, T_, C_, self_) hipLaunchKernelGGL((k_scan_hits2<S_, T_, C_>), dim3(grid), dim3(T_), 0, st, lo, i0, i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), \
                            c.wctx.as<LzWctx>(), sk, sv, n, off, base, P, Q, lut, tagged, tasks, ntk, region_cap, self_)
     if (c.self.mode != LZ_SELF_OFF) LZ_FUSED_LAUNCH(true, 512, 2560, c.self);
-    else if (tpb == 512)            LZ_FUSED_LAUNCH(false, 512, 2560, LzSelfDev{});
-    else if (tpb == 768)            LZ_FUSED_LAUNCH(false, 768, 1024, LzSelfDev{});
     else                            LZ_FUSED_LAUNCH(false, 1024, 512, LzSelfDev{});
 #undef LZ_FUSED_LAUNCH
     c.timer.end(st);

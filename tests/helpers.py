@@ -2,6 +2,8 @@
 import json
 import os
 import subprocess
+import sys
+import time
 import numpy as np
 
 from oracle import lzo
@@ -11,6 +13,62 @@ from lavparse import parse_lav
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DEFAULT_SEED = "1110100110010101111"
+
+
+COUNTERS = ("words", "raw_hits", "extensions", "bp_extended")
+
+# ---- GPU tests that vary a process setting of the library (lastz_amd/csrc/lz_settings.hpp: read once per process)
+
+GPU_CHILD = os.path.join(ROOT, "tests", "gpu_child.py")
+# what a child must not inherit from the caller's environment; a run's own settings are applied on top
+CHILD_SCRUB = ("LZGPU_FUSED_SCAN", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP")
+
+
+def search_strands(g, search, queries):
+    """one run of a cases module (gpu_child.py): search(q) per strand -> the HSP arrays and the scan mode each search took"""
+    hsps, modes = [], []
+    for q in queries:
+        hsps.append(search(q)); modes.append(g.last_scan_mode())
+    return {"hsps": hsps, "scan_modes": modes}
+
+
+def run_gpu_children(tmpdir, runs):
+    """runs: [(key, cases module, cases, environment, time limit, scan mode or None)] -> {key: (arrays, meta)} in gpu_child.py's format.
+    One fresh child process per run, one after the other, each under its own time limit; the first that fails raises --
+    nothing more is started on the GPU after a fault."""
+    out = {}
+    for key, module, cases, settings, limit, mode in runs:
+        env = {k: v for k, v in os.environ.items() if k not in CHILD_SCRUB}
+        env.update(settings)
+        fn = os.path.join(str(tmpdir), key + ".npz")
+        t0 = time.perf_counter()
+        forced = [] if mode is None else ["--scan-mode", str(mode)]
+        r = subprocess.run([sys.executable, GPU_CHILD, fn, module] + forced + list(cases),
+                           capture_output=True, text=True, timeout=limit, env=env)
+        assert r.returncode == 0 and "gpu child ok" in r.stdout, "%s (exit %s): %s%s" % (key, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
+        z = np.load(fn)
+        out[key] = (z, json.loads(str(z["meta"])))
+        print("\ngpu child %-20s %2d cases  %.1f s wall" % (key, len(cases), time.perf_counter() - t0))
+    return out
+
+
+def gpu_aligns(gpu, t, queries, **kw):
+    """whole hot path on the GPU: table -> HSPs -> gapped, per query and strand, as lastz drives it
+    -> [(query number, strand, alignments, edit ops)], the counters"""
+    from lastz_amd import lzgpu
+    sub, masked = scoring()
+    gpu.table_prepare(t, gpu.seed(), lzo.upper_nuc_to_bits())
+    out = []
+    gpu.counters_reset()
+    for ci, q in enumerate(queries):
+        for _, rev, qq in strands(q):
+            hsps = gpu.seed_hit_search(masked, q=qq)
+            segs = np.zeros(len(hsps), dtype=lzgpu.SEG_DTYPE)
+            segs["pos1"] = hsps["pos1"] - hsps["length"]; segs["pos2"] = hsps["pos2"] - hsps["length"]
+            segs["length"] = hsps["length"]; segs["s"] = hsps["score"]; segs["id"] = rev
+            al, ops = gpu.gapped_extend(sub, segs, q=qq, **kw)
+            out.append((ci + 1, rev, al, ops))
+    return out, gpu.counters()
 
 
 def scoring():

@@ -126,6 +126,30 @@ def seed_case(name, gpu=False, specials=False):
     return t, q, masked, dict(xdrop=xdrop, hsp_threshold=thr), mode
 
 
+CHUNK_CAPACITY = 20_000
+
+
+def split_case(case):
+    """a case of tests/gpu_child.py: a row's name, with `.s` for its variant with special bytes or `.c` for the run in chunks of
+    at most CHUNK_CAPACITY hits -> (name, specials, chunks)"""
+    name, _, variant = case.partition(".")
+    return name, variant == "s", variant == "c"
+
+
+def run(g, case):
+    import helpers as H
+    name, specials, chunks = split_case(case)
+    t, q, masked, kw, _ = seed_case(name, gpu=True, specials=specials)
+    g.table_prepare(t, g.seed(H.DEFAULT_SEED, 1), lzo.upper_nuc_to_bits())
+    if chunks:
+        g.set_hit_capacity(CHUNK_CAPACITY)
+    try:
+        yield H.search_strands(g, lambda qq: g.seed_hit_search(masked, q=qq, **kw), [qq for _, _, qq in H.strands(q)])
+    finally:
+        if chunks:
+            g.set_hit_capacity(1 << 28)
+
+
 def with_specials(t, q, seed=4):
     """N runs, lower case, IUPAC bytes single and in runs sprinkled into both sequences (as
     test_emul_vs_oracle.test_lut_scans_through_special_bytes_that_do_not_end_a_scan does, thinner: the cases still need HSPs)"""

@@ -154,6 +154,30 @@ def sequence(name):
     return v, seps, s
 
 
+WHOLE = 1 << 28                                     # the hit capacity that chunks nothing here
+
+
+def run(g, name):
+    """tests/gpu_child.py: one run per hit capacity of the case"""
+    import helpers as H
+    from oracle import lzo
+    c = CASES[name]
+    v, seps, _ = sequence(name)
+    _, masked = H.scoring()
+    for capacity in c["capacities"]:
+        g.set_scan_mode(c["force_mode"])
+        g.set_hit_capacity(capacity or WHOLE)
+        try:
+            g.table_prepare(v, g.seed(c["pattern"], c["trans"]), lzo.upper_nuc_to_bits(), step=c["step"])
+            run = H.search_strands(g, lambda strand: g.seed_hit_search_self(
+                masked, q=v if strand == "+" else minus(v, seps), same_strand=(strand == "+"), band_width=c["band"], sep1=seps or None,
+                sep2=seps or None, xdrop=c["xdrop"], hsp_threshold=c["hsp_threshold"], entropic=c["entropic"], extend=c["extend"]), c["strands"])
+        finally:
+            g.set_hit_capacity(WHOLE)
+            g.set_scan_mode(0)
+        yield dict(run, capacity=capacity)
+
+
 def record_names(seps):
     return ["r%d" % k for k in range(len(seps) - 1)] if seps else ["s"]
 

@@ -6,21 +6,13 @@ several chunks, tiny task regions and a self-comparison; mode 0 everywhere; and 
 
 Every setting runs in a fresh child process (the switches are read once) under its own time limit, one after the
 other; the first child that fails ends the series -- nothing more is started on the GPU after a fault.  Needs an MI355X."""
-import json
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 
 import helpers as H
 
 pytestmark = pytest.mark.gpu
-CHILD = os.path.join(H.ROOT, "tests", "fused_scan_child.py")
 MAIN = ["synth3", "synth4", "synth2m", "tandem", "two_transitions", "chunks", "self_plain"]
 SMALL_REGIONS = ["synth3", "tandem"]
-COUNTERS = ("words", "raw_hits", "extensions", "bp_extended")
 #          key                      cases          fused  extra environment
 RUNS = [("fused",                   MAIN,          "1",   {}),
         ("split",                   MAIN,          "0",   {}),
@@ -30,18 +22,9 @@ RUNS = [("fused",                   MAIN,          "1",   {}),
 
 @pytest.fixture(scope="module")
 def runs(gpu, tmp_path_factory):
-    d = tmp_path_factory.mktemp("fused")
-    out = {}
-    for key, cases, fused, extra in RUNS:
-        env = dict(os.environ); env.update(extra); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY"):
-            env.pop(k, None)
-        fn = str(d / (key + ".npz"))
-        r = subprocess.run([sys.executable, CHILD, fn] + cases, capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0 and "fused child ok" in r.stdout, key + ": " + r.stdout[-1000:] + r.stderr[-3000:]
-        z = np.load(fn)
-        out[key] = (z, json.loads(str(z["meta"])))
-    return out
+    out = H.run_gpu_children(tmp_path_factory.mktemp("fused"),
+                             [(key, "fused_scan_cases", cases, dict(extra, LZGPU_FUSED_SCAN=fused), 600, None) for key, cases, fused, extra in RUNS])
+    return {key: (z, {name: m[0] for name, m in meta.items()}) for key, (z, meta) in out.items()}     # one run per case
 
 
 @pytest.mark.parametrize("a,b,cases", [("fused", "split", MAIN), ("fused_small_regions", "split_small_regions", SMALL_REGIONS),
@@ -50,10 +33,10 @@ def test_same_hsps_and_counters(runs, a, b, cases):
     (za, ma), (zb, mb) = runs[a], runs[b]
     for name in cases:
         for k in (0, 1):
-            x, y = za["%s.%d" % (name, k)], zb["%s.%d" % (name, k)]
+            x, y = za["%s/0/%d" % (name, k)], zb["%s/0/%d" % (name, k)]
             assert len(x) == len(y) and (x == y).all(), (name, k)
-        assert sum(len(za["%s.%d" % (name, k)]) for k in (0, 1)) > 0, name
-        for c in COUNTERS:
+        assert sum(len(za["%s/0/%d" % (name, k)]) for k in (0, 1)) > 0, name
+        for c in H.COUNTERS:
             assert ma[name]["counters"][c] == mb[name]["counters"][c], (name, c)
 
 
@@ -61,7 +44,7 @@ def test_mode_0_and_the_path_that_ran(runs):
     for key, cases, fused, _ in RUNS:
         meta = runs[key][1]
         for name in cases:
-            assert meta[name]["scan_mode"] == 0, (key, name)
+            assert meta[name]["scan_modes"] == [0, 0], (key, name)
             la = meta[name]["launches"]
             assert la.get("k_scan_hits", 0) > 0 and la.get("k_partition", 0) > 0, (key, name)
             if fused == "1":

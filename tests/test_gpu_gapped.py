@@ -15,21 +15,9 @@ CTB = lzo.upper_nuc_to_bits()
 
 
 def _gpu_blocks(gpu, t, queries, **kw):
-    """whole hot path on the GPU: table -> HSPs -> gapped, per query and strand, as lastz drives it"""
-    sub, masked = H.scoring()
-    gpu.table_prepare(t, gpu.seed(), CTB)
-    out = []
-    gpu.counters_reset()
-    for ci, q in enumerate(queries):
-        for _, rev, qq in H.strands(q):
-            hsps = gpu.seed_hit_search(masked, q=qq)
-            segs = np.zeros(len(hsps), dtype=lzgpu.SEG_DTYPE)
-            segs["pos1"] = hsps["pos1"] - hsps["length"]; segs["pos2"] = hsps["pos2"] - hsps["length"]
-            segs["length"] = hsps["length"]; segs["s"] = hsps["score"]; segs["id"] = rev
-            al, ops = gpu.gapped_extend(sub, segs, q=qq, **kw)
-            if len(al):
-                out.append((ci + 1, rev, H.blocks_of(al, ops)))
-    return out, gpu.counters()
+    """whole hot path on the GPU (helpers.gpu_aligns), as the blocks of a LAV"""
+    out, counters = H.gpu_aligns(gpu, t, queries, **kw)
+    return [(ci, rev, H.blocks_of(al, ops)) for ci, rev, al, ops in out if len(al)], counters
 
 
 def test_base_test_default_lav(gpu):
@@ -386,3 +374,53 @@ def test_same_alignments_after_shutdown_and_init(gpu):
     al2, ops2, _, c2, n2 = one_pass()                            # under the defaults: fewer launches (no retries), other rounds
     assert (al2 == oal).all() and (ops2 == oops).all()
     assert c2["gapped_extensions"] != c0["gapped_extensions"] and n2 < n0
+
+
+HORIZON_CHILD = ("import json, sys\n"
+                 "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+                 "import numpy as np\n"
+                 "import helpers as H\n"
+                 "from lastz_amd import lzgpu\n"
+                 "g = lzgpu.Lib(); g.init(); g.profile_enable(True)\n"
+                 "t, q = H.load_case('adversarial')\n"
+                 "runs, c = H.gpu_aligns(g, t[9000:14500], [q[29500:34000]])\n"
+                 "launches = {k: v['launches'] for k, v in g.profile().items()}\n"
+                 "g.shutdown()\n"
+                 "arrays = {}\n"
+                 "for _, rev, al, ops in runs: arrays['al%%d' %% rev] = al; arrays['ops%%d' %% rev] = ops\n"
+                 "np.savez(sys.argv[1], meta=np.array(json.dumps({'launches': launches, 'dp_cells': c['dp_cells'], 'anchors_extended': c['anchors_extended']})), **arrays)\n"
+                 "print('horizon child ok')\n" % (H.ROOT, os.path.join(H.ROOT, "tests")))
+
+
+def test_a_sweep_that_passes_its_piece_horizon_is_run_again(gpu, tmp_path):
+    """LZGPU_DP_HORIZON=97 (a process setting: a fresh child) on the obstacle-course slice of tests/test_emul_gapped.py: bounds hop, die and
+    mask across the 97-row horizon of a DP's pieces, the sweep stops there (LZ_DP_PIECE_SLOT) and is run again with pieces up to a
+    farther one.  Alignments, edit scripts and the two counters are the oracle's, as in a child without the switch, and the
+    profile shows the re-runs: more k_ydrop + k_ydrop_n launches than that child made."""
+    import json, subprocess, sys
+    t, q = H.load_case("adversarial")
+    t, q = t[9000:14500], q[29500:34000]
+    sub, masked = H.scoring()
+    tab = lzo.Table(t, lzo.seed())
+    want, cells, extended = {}, 0, 0
+    for _, rev, qq in H.strands(q):
+        hsps, _ = lzo.seed_hit_search(tab, qq, masked)
+        oal, oops, ost = lzo.gapped_extend(t, qq, sub, lzo.reduce_to_points(t, qq, sub, lzo.hsps_to_segments(hsps, rev)))
+        want[rev] = (oal, oops); cells += ost["dp_cells"]; extended += ost["anchors_extended"]
+    assert sum(len(oal) for oal, _ in want.values()) > 0
+    launches = {}
+    for key, horizon in (("short", "97"), ("default", None)):        # (the second starts only if the first came back well)
+        env = {k: v for k, v in os.environ.items() if k != "LZGPU_DP_HORIZON"}
+        if horizon:
+            env["LZGPU_DP_HORIZON"] = horizon
+        fn = str(tmp_path / (key + ".npz"))
+        r = subprocess.run([sys.executable, "-c", HORIZON_CHILD, fn], capture_output=True, text=True, timeout=120, env=env)
+        assert r.returncode == 0 and "horizon child ok" in r.stdout, "%s (exit %s): %s%s" % (key, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
+        z = np.load(fn); meta = json.loads(str(z["meta"]))
+        for rev, (oal, oops) in want.items():
+            al, ops = z["al%d" % rev], z["ops%d" % rev]
+            assert len(al) == len(oal) and (al == oal).all() and (ops == oops).all(), (key, rev)
+        assert meta["dp_cells"] == cells and meta["anchors_extended"] == extended, (key, meta)
+        launches[key] = meta["launches"].get("k_ydrop", 0) + meta["launches"].get("k_ydrop_n", 0)
+        print(key, "k_ydrop + k_ydrop_n launches", launches[key], meta["launches"])
+    assert launches["short"] > launches["default"] > 0, launches

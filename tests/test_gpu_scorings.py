@@ -16,23 +16,16 @@ first child that fails ends the series -- nothing more is started on the GPU aft
 
 DP stage: every row of scorings.DP_CASES with either build of the DP kernel forced, in this process: alignments, edit
 scripts, and which of k_ydrop / k_ydrop_n / k_ydrop_wide ran.  One window search under the matrix `eight`.  Needs an MI355X."""
-import json
 import os
-import subprocess
-import sys
-import time
 
-import numpy as np
 import pytest
 
 from oracle import lzo
 from lastz_amd import lzgpu
 import helpers as H
 import scorings as S
-import scorings_child as Ch
 
 pytestmark = pytest.mark.gpu
-CHILD = os.path.join(H.ROOT, "tests", "scorings_child.py")
 CTB = lzo.upper_nuc_to_bits()
 ALL = list(S.SEED_CASES)
 #          key       cases                                                   scan mode  fused
@@ -45,20 +38,9 @@ RUNS = [("fused",   ALL + [n + ".s" for n in ALL],                           0, 
 
 @pytest.fixture(scope="module")
 def runs(gpu, tmp_path_factory):
-    d = tmp_path_factory.mktemp("scorings")
-    out = {}
-    for key, cases, mode, fused in RUNS:
-        env = dict(os.environ); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
-            env.pop(k, None)
-        fn = str(d / (key + ".npz"))
-        t0 = time.time()
-        r = subprocess.run([sys.executable, CHILD, fn, str(mode)] + cases, capture_output=True, text=True, timeout=300, env=env)
-        assert r.returncode == 0 and "scorings child ok" in r.stdout, key + ": " + r.stdout[-1000:] + r.stderr[-3000:]
-        z = np.load(fn)
-        out[key] = (z, json.loads(str(z["meta"])))
-        print("scorings child %-6s %2d cases  %.1f s wall" % (key, len(cases), time.time() - t0))
-    return out
+    out = H.run_gpu_children(tmp_path_factory.mktemp("scorings"),
+                             [(key, "scorings", cases, {"LZGPU_FUSED_SCAN": fused}, 300, mode) for key, cases, mode, fused in RUNS])
+    return {key: (z, {case: m[0] for case, m in meta.items()}) for key, (z, meta) in out.items()}     # one run per case
 
 
 @pytest.fixture(scope="module")
@@ -70,11 +52,11 @@ def oracle():
         if (name, specials) not in cache:
             t, q, masked, kw, mode = S.seed_case(name, gpu=True, specials=specials)
             tab = lzo.Table(t, lzo.seed(H.DEFAULT_SEED, 1))
-            hs, tot = [], dict.fromkeys(Ch.COUNTERS, 0)
+            hs, tot = [], dict.fromkeys(H.COUNTERS, 0)
             for _, _, qq in H.strands(q):
                 h, st = lzo.seed_hit_search(tab, qq, masked, **kw)
                 hs.append(h)
-                for c in Ch.COUNTERS:
+                for c in H.COUNTERS:
                     tot[c] += st[c]
             cache[(name, specials)] = (hs, tot, mode)
         return cache[(name, specials)]
@@ -84,14 +66,14 @@ def oracle():
 @pytest.mark.parametrize("key,case", [(key, case) for key, cases, _, _ in RUNS for case in cases])
 def test_hsps_and_counters_equal_the_oracle(runs, oracle, key, case):
     z, meta = runs[key]
-    name, specials, _ = Ch.split_case(case)
+    name, specials, _ = S.split_case(case)
     want, tot, _ = oracle(name, specials)
     for k in (0, 1):
-        got = z["%s/%d" % (case, k)]
+        got = z["%s/0/%d" % (case, k)]
         print(key, case, "strand", k, "HSPs", len(got), "oracle", len(want[k]))
         assert len(want[k]) > 0, (key, case, k)                 # the row has HSPs on each strand
         assert len(got) == len(want[k]) and (got == want[k]).all(), (key, case, k)
-    for c in Ch.COUNTERS:
+    for c in H.COUNTERS:
         assert meta[case]["counters"][c] == tot[c], (key, case, c)
 
 
@@ -99,7 +81,7 @@ def test_the_path_that_ran(runs, oracle):
     for key, cases, forced, fused in RUNS:
         meta = runs[key][1]
         for case in cases:
-            name, specials, _ = Ch.split_case(case)
+            name, specials, _ = S.split_case(case)
             mode = max(forced, oracle(name, specials)[2])       # the row's expected mode; 1 at least with special bytes
             la = meta[case]["launches"]
             print(key, case, "scan modes", meta[case]["scan_modes"], "expected", mode,

@@ -18,12 +18,7 @@ switch is read once per process.  Each child has its own time limit; the first t
 more is started on the GPU after a fault, and nothing is tried again.  The entry point's declines are checked in
 process.  Needs an MI355X."""
 import json
-import os
-import subprocess
-import sys
-import time
 
-import numpy as np
 import pytest
 
 from oracle import lzo
@@ -32,7 +27,6 @@ import helpers as H
 import self_cases as S
 
 pytestmark = pytest.mark.gpu
-CHILD = os.path.join(H.ROOT, "tests", "self_matrix_child.py")
 CTB = lzo.upper_nuc_to_bits()
 #          key       cases             LZGPU_FUSED_SCAN
 RUNS = [("fused",   list(S.CASES),    "1"),
@@ -42,23 +36,13 @@ PAIRS = [(key, name) for key, cases, _ in RUNS for name in cases]
 
 @pytest.fixture(scope="module")
 def runs(gpu, tmp_path_factory):
-    d = tmp_path_factory.mktemp("self_matrix")
-    out = {}
-    for key, cases, fused in RUNS:
-        env = dict(os.environ); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
-            env.pop(k, None)
-        fn = str(d / (key + ".npz"))
-        t0 = time.perf_counter()
-        r = subprocess.run([sys.executable, CHILD, fn] + cases, capture_output=True, text=True, timeout=300, env=env)
-        wall = time.perf_counter() - t0
-        assert r.returncode == 0 and "self matrix child ok" in r.stdout, key + ": " + r.stdout[-1000:] + r.stderr[-3000:]
-        z = np.load(fn)
-        out[key] = (z, json.loads(str(z["meta"])))
-        print("\nself matrix child %-5s %6.2f s, %d cases" % (key, wall, len(cases)))
+    out = H.run_gpu_children(tmp_path_factory.mktemp("self_matrix"),
+                             [(key, "self_cases", cases, {"LZGPU_FUSED_SCAN": fused}, 300, None) for key, cases, fused in RUNS])
+    for key, cases, _ in RUNS:
+        print("\nself matrix child %s" % key)
         for name in cases:
             for m in out[key][1][name]:
-                print("  %-16s capacity %-6s mode %d  %6.3f s  %s" % (name, m["capacity"], m["scan_mode"], m["seconds"],
+                print("  %-16s capacity %-6s mode %d  %6.3f s  %s" % (name, m["capacity"], m["scan_modes"][-1], m["seconds"],
                       " ".join("%s=%d" % kv for kv in sorted(m["launches"].items()))))
     return out
 
@@ -84,7 +68,7 @@ def test_hsps_and_counters_equal_the_oracle(runs, oracle, key, name):
     assert len(meta[name]) == len(S.CASES[name]["capacities"])
     for r, m in enumerate(meta[name]):
         for k in range(len(S.CASES[name]["strands"])):
-            got = z["%s.%d.%d" % (name, r, k)]
+            got = z["%s/%d/%d" % (name, r, k)]
             assert len(got) == len(want[k]) and (got == want[k]).all(), (key, name, m["capacity"], k)
         for c in ("words", "raw_hits") if name == "plainhits" else S.COUNTERS:
             assert m["counters"][c] == tot[c], (key, name, m["capacity"], c)
@@ -97,7 +81,7 @@ def test_the_path_that_ran(runs, key, name):
     fused = key == "fused"
     for m in runs[key][1][name]:
         la = m["launches"]
-        assert m["scan_mode"] == c["mode"], (key, name, m)
+        assert m["scan_modes"] == [c["mode"]] * len(c["strands"]), (key, name, m)
         assert la.get("k_count_hits", 0) > 0, (key, name, la)
         if fused and c["mode"] == 0:
             assert la.get("k_build_wctx", 0) > 0 and la.get("k_fill_hits", 0) == 0, (key, name, la)

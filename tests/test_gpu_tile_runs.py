@@ -16,20 +16,13 @@ test_gpu_seed.py's 2 Mbp pairs; a window that spans several blocks is tests/test
 
 Every setting runs in a fresh child process (LZGPU_FUSED_SCAN is read once) under its own time limit, one after the
 other; the first child that fails ends the series -- nothing more is started on the GPU after a fault.  Needs an MI355X."""
-import json
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 
 from oracle import lzo
 import helpers as H
-import tile_runs_child as Ch
+import tile_runs_cases as Ch
 
 pytestmark = pytest.mark.gpu
-CHILD = os.path.join(H.ROOT, "tests", "tile_runs_child.py")
 TILE, S2_TILE = 16384, 5376
 #          key       cases                                    scan mode  fused
 RUNS = [("fused",   ["small", "tandem", "sparse", "chunks"],  0,         "1"),
@@ -39,18 +32,9 @@ RUNS = [("fused",   ["small", "tandem", "sparse", "chunks"],  0,         "1"),
 
 @pytest.fixture(scope="module")
 def runs(gpu, tmp_path_factory):
-    d = tmp_path_factory.mktemp("tile_runs")
-    out = {}
-    for key, cases, mode, fused in RUNS:
-        env = dict(os.environ); env["LZGPU_FUSED_SCAN"] = fused
-        for k in ("LZGPU_FILL_SHUFFLE", "LZGPU_SCAN_MODE", "LZGPU_HIT_CAPACITY", "LZGPU_TASK_REGION_CAP"):
-            env.pop(k, None)
-        fn = str(d / (key + ".npz"))
-        r = subprocess.run([sys.executable, CHILD, fn, str(mode)] + cases, capture_output=True, text=True, timeout=300, env=env)
-        assert r.returncode == 0 and "tile runs child ok" in r.stdout, key + ": " + r.stdout[-1000:] + r.stderr[-3000:]
-        z = np.load(fn)
-        out[key] = (z, json.loads(str(z["meta"])))
-    return out
+    out = H.run_gpu_children(tmp_path_factory.mktemp("tile_runs"),
+                             [(key, "tile_runs_cases", cases, {"LZGPU_FUSED_SCAN": fused}, 300, mode) for key, cases, mode, fused in RUNS])
+    return {key: (z, {name: m[0] for name, m in meta.items()}) for key, (z, meta) in out.items()}     # one run per case
 
 
 @pytest.fixture(scope="module")
@@ -61,11 +45,11 @@ def oracle():
     for name in ("small", "tandem", "sparse"):
         t, q = Ch.PAIRS[name][0]()
         tab = lzo.Table(t, lzo.seed(H.DEFAULT_SEED, 1))
-        hs, tot = [], dict.fromkeys(Ch.COUNTERS, 0)
+        hs, tot = [], dict.fromkeys(H.COUNTERS, 0)
         for _, _, qq in H.strands(q):
             h, st = lzo.seed_hit_search(tab, qq, masked)
             hs.append(h)
-            for c in Ch.COUNTERS:
+            for c in H.COUNTERS:
                 tot[c] += st[c]
         out[name] = (hs, tot)
     out["chunks"] = out["sparse"]
@@ -77,10 +61,10 @@ def test_hsps_and_counters_equal_the_oracle(runs, oracle, key, name):
     z, meta = runs[key]
     want, tot = oracle[name]
     for k in (0, 1):
-        got = z["%s.%d" % (name, k)]
+        got = z["%s/0/%d" % (name, k)]
         assert len(got) == len(want[k]) and (got == want[k]).all(), (key, name, k)
     assert sum(len(h) for h in want) > 0
-    for c in Ch.COUNTERS:
+    for c in H.COUNTERS:
         assert meta[name]["counters"][c] == tot[c], (key, name, c)
 
 
@@ -89,7 +73,7 @@ def test_the_path_that_ran(runs):
         meta = runs[key][1]
         for name in cases:
             la = meta[name]["launches"]
-            assert meta[name]["scan_mode"] == mode, (key, name)
+            assert meta[name]["scan_modes"] == [mode, mode], (key, name)
             assert "k_hist" not in la, (key, name, la)
             for k in ("k_partition", "k_hist_scan", "k_settle2"):
                 assert la.get(k, 0) > 0, (key, name, k, la)

@@ -1,25 +1,12 @@
-"""Child process of tests/test_gpu_tile_runs.py: runs the cases below under the scan mode given on the command line and
-whatever LZGPU_FUSED_SCAN the parent put into the environment (read once per process) and saves, per case, the HSP
-arrays of both strands, the counters, the scan mode and the launches the profile saw.
-
-    python tests/tile_runs_child.py OUT.npz MIN_SCAN_MODE CASE [CASE ...]
-"""
-import json
-import os
-import sys
-
+"""The pairs of tests/test_gpu_tile_runs.py, run by tests/gpu_child.py under the scan mode on its command line and whatever
+LZGPU_FUSED_SCAN the parent put into its environment."""
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from lastz_amd import lzgpu, seqio                 # noqa: E402
-from oracle import lzo                              # noqa: E402
-import helpers as H                                 # noqa: E402
+from lastz_amd import seqio
+from oracle import lzo
+import helpers as H
 
 CTB = lzo.upper_nuc_to_bits()
-COUNTERS = ("words", "raw_hits", "extensions", "bp_extended")
 SPARSE_LEN = 20_000
 CHUNK_CAPACITY = 300_000
 
@@ -53,7 +40,7 @@ def sparse_pair():
 PAIRS = {"small": (small_pair, None), "tandem": (tandem_pair, None), "sparse": (sparse_pair, None), "chunks": (sparse_pair, CHUNK_CAPACITY)}
 
 
-def run_case(g, name):
+def run(g, name):
     make, capacity = PAIRS[name]
     t, q = make()
     _, masked = H.scoring()
@@ -61,30 +48,7 @@ def run_case(g, name):
     if capacity:
         g.set_hit_capacity(capacity)
     try:
-        return [g.seed_hit_search(masked, q=qq) for _, _, qq in H.strands(q)]
+        yield H.search_strands(g, lambda qq: g.seed_hit_search(masked, q=qq), [qq for _, _, qq in H.strands(q)])
     finally:
         if capacity:
             g.set_hit_capacity(1 << 28)
-
-
-def main():
-    out, mode, names = sys.argv[1], int(sys.argv[2]), sys.argv[3:]
-    g = lzgpu.Lib(); g.init()
-    g.profile_enable(True)
-    g.set_scan_mode(mode)
-    res, meta = {}, {}
-    for name in names:
-        g.profile_reset(); g.counters_reset()
-        hs = run_case(g, name)
-        c = g.counters()
-        for k, h in enumerate(hs):
-            res["%s.%d" % (name, k)] = h
-        meta[name] = {"counters": {k: c[k] for k in COUNTERS}, "scan_mode": g.last_scan_mode(),
-                      "launches": {k: v["launches"] for k, v in g.profile().items()}}
-    g.shutdown()
-    np.savez(out, meta=np.array(json.dumps(meta)), **res)
-    print("tile runs child ok")
-
-
-if __name__ == "__main__":
-    main()
