@@ -1,7 +1,7 @@
 // lz_common.hpp -- shared POD types and the per-thread ("lane") logic of the seed stage.
 //
 // The functions marked LZ_HD are what one GPU thread executes; the __global__ kernels in
-// seed_kernels.hip are thin wrappers that map threadIdx/blockIdx onto them.  They are written
+// the seed stage's *_kernels.hip files are thin wrappers that map threadIdx/blockIdx onto them.  They are written
 // against plain pointers so that tests/emul/ can also run them on the host (one "lane" at a
 // time) to check the decomposition logic without a GPU.  That host harness is test
 // infrastructure; the product library never executes these functions on the CPU.
@@ -396,7 +396,7 @@ LZ_HD bool lz_scan_right16(const s32* score_tab, const s32* tab8, bool fast, s32
 // dependent memory round trips per hit: key, blocks) and scanned; most hits end inside them.
 // lz_scan_continue: a scan that is still going continues block by block, up to the cap.  The two
 // scans of a hit are independent (loop 2 restarts at the seed end, :2663-2682), so the kernel hands
-// the unfinished ones to other lanes as separate tasks (seed_kernels.hip); lz_probe_hit is the plain
+// the unfinished ones to other lanes as separate tasks (scan_kernels.hip); lz_probe_hit is the plain
 // composition.  (The 64 bytes of padding around the sequences cover blocks that reach over an end.)
 #ifndef LZ_PROBE_AHEAD_L
 #define LZ_PROBE_AHEAD_L 3

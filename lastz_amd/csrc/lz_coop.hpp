@@ -15,7 +15,7 @@
 // Results are bit-identical to the serial loops for any matrix and any xDrop >= 0.
 //
 // The per-lane pieces are LZ_HD (device + tests/emul); the cross-lane glue exists twice: wave intrinsics in
-// seed_kernels.hip, plain loops over the lanes in lz_coop_scan_host() below (test infrastructure).
+// settle_kernels.hip, plain loops over the lanes in lz_coop_scan_host() below (test infrastructure).
 #pragma once
 #include "lz_common.hpp"
 

@@ -87,7 +87,7 @@ struct LzCtx {
 
     // ---- seed-search scratch
     DevBuf cnt, off, pk;            // per query position: raw-hit count (u32), exclusive scan (u64), packed word (u32)
-    DevBuf wiv, wsk, wsv;           // position index; (block of positions | word, position) sorted by that key (seed_kernels.hip: k_pack_words)
+    DevBuf wiv, wsk, wsv;           // position index; (block of positions | word, position) sorted by that key (enum_kernels.hip: k_pack_words)
     DevBuf blk_start;               // where each block of positions begins in the sorted list
     std::vector<u64> blk_start_host;
     u32 blk_shift = 0, blk_count = 1;
@@ -118,6 +118,7 @@ struct LzCtx {
     struct DpBufs { DevBuf jobs, ids, res, tab, tb, rows, ops, ops_off, ops_out, pieces, rings, sel_jobs, sel_res, problems; } dp;
     DevBuf win_jobs, win_scratch, win_out, win_count;
     bool win_attr_set = false;        // k_window_search's dynamic-LDS attribute has been set on this device context (lzgpu_shutdown clears it)
+    bool settle_attr_set = false;     // likewise k_settle2's
     u64 dp_longest[4] = { 0, 0, 0, 0 };   // lzgpu_dp_longest: rows, cells, sweep and traceback ticks of the DP that swept the most rows since the last reset
     // the two settings below keep their value across shutdown + init, as hit_capacity does
     u32 dp_slot_tb = 8u << 20;        // lzgpu_set_dp_slot: the uniform traceback slot (bytes) per DP
@@ -156,7 +157,7 @@ struct LzCtx {
         pinned = nullptr; pinned_words = 0;
         have_table = false; wctx_gen = 0; wctx_code_key = 0;
         score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
-        win_attr_set = false;
+        win_attr_set = false; settle_attr_set = false;
     }
 };
 
@@ -166,30 +167,32 @@ int lz_fail(int code, const char* fmt, ...);
 #define LZ_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) \
     return lz_fail(LZGPU_ERR_HIP, "%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); } while (0)
 
-// ---- launchers implemented in seed_kernels.hip (all asynchronous on ctx.stream) ----
+// ---- the seed stage's launchers: all asynchronous on c.stream (lzk_encode: or the stream it is given).  A launcher is passed what
+// varies per call -- the chunk, the kernels' parameters, the mode -- and reads the buffers that are members of LzCtx from c. ----
+struct LzChunk; struct LzLutParams;                  // lz_host.hpp, lz_lut.hpp
+#include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
+// seq_kernels.hip
 int lzk_encode(LzCtx& c, const u8* raw, u8* code, u32 len, const u8* cls256_dev, hipStream_t st = nullptr, KernelTimer* timer = nullptr);   // defaults: c.stream, c.timer
 int lzk_pack_nibbles(LzCtx& c, const u8* code_alloc, u8* nib, size_t nbytes);
-int lzk_table_build(LzCtx& c);
-int lzk_table_export(LzCtx& c, u32* last_dev, u32* prev_dev, u32 prev_entries);
-int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi, u32* cnt, u32* pk, u32* iv, u32* sk, u32* sv, u64* valid_words_dev);   // honours c.n_owners / c.owner and c.self
-int lzk_scan_counts(LzCtx& c, const u32* cnt, u64* off, u32 n);
-int lzk_sample_offsets(LzCtx& c, const u64* off, const u32* cnt, u32 n, u32 stride, u32 ns, u64* out);
-int lzk_fill_hits(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64* keys, hipStream_t st);   // likewise
-int lzk_hsp_match_counts(LzCtx& c, const LzHspRec* recs, const u32* n_rec_dev, u32 cap, u32 launch_for,
-                         const u8* traw, const u8* qraw, const u8* tcode, const u8* qcode, u32* counts, hipStream_t s);
-struct LzLutParams; struct LzLutEntry;
-#include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
 int lzk_pack2(LzCtx& c, const u8* code_base, const u8* raw_base, u32 len, u8* two, u8* spc, u32 nmask, u32* flags256);
 int lzk_overlap32(LzCtx& c, const u8* src, u8* dst, size_t nblocks);
-int lzk_hist_scan(LzCtx& c, u64 n, u32* hist, u32* part, u32* bin_base, hipStream_t st);      // after the partition of the chunk
-int lzk_scan_reserve(LzCtx& c, int mode, u64 max_n);
-int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams& Q, const u64* keys, u64 n,
-                  const s32* score_tab, const LzLutEntry* lut, u8* bins, hipStream_t st);     // -> c.summ, and the partition byte of every hit -> bins
-int lzk_partition(LzCtx& c, bool tagged, u64* recs, const u32* summ, u64 n, u32* hist, u32* run_addr, hipStream_t st);   // keys + summaries (or tagged records: summ unused) -> records, in place
-// the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records instead of keys / summaries / partition bytes
+// table_kernels.hip
+int lzk_table_build(LzCtx& c);
+int lzk_table_export(LzCtx& c, u32* last_dev, u32* prev_dev, u32 prev_entries);
 int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
+// enum_kernels.hip (the query positions [lo, hi), n = hi - lo of them: c.cnt, c.off, c.pk, c.wiv, c.wsk, c.wsv, sized by the caller)
+int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi);   // honours c.n_owners / c.owner and c.self
+int lzk_scan_counts(LzCtx& c, u32 n);
+int lzk_sample_offsets(LzCtx& c, u32 n, u32 stride, u32 ns);     // -> c.pinned
+int lzk_fill_hits(LzCtx& c, u32 lo, const LzChunk& ch, u32 n);   // likewise; -> c.keys
+// scan_kernels.hip
+int lzk_scan_reserve(LzCtx& c, int mode, u64 max_n);
+int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams& Q, u64 n);   // c.keys -> c.summ, and the partition byte of every hit -> c.bins
+// the fused path of scan mode 0 (k_scan_hits2): enumeration + phase A in one launch, tagged records in c.keys instead of keys / summaries / partition bytes
 int lzk_fused_reserve(LzCtx& c, u64 max_n);
-int lzk_scan_fused(LzCtx& c, u32 lo, u32 i0, u32 i1, const u32* sk, const u32* sv, u32 n, const u64* off, u64 base, u64 n_hits,
-                   const LzExtendParams& P, const LzLutParams& Q, const LzLutEntry* lut, u64* tagged, hipStream_t st);
-int lzk_settle(LzCtx& c, const LzExtendParams& P, const u64* recs, u64 n, const u32* hist, const u32* hist_part, const u32* run_addr,
-               const u32* bin_base, u32* diag_end, const s32* score_tab, LzHspRec* out, u32* out_count, u32 out_cap, u64* counters, hipStream_t s);
+int lzk_scan_fused(LzCtx& c, u32 lo, const LzChunk& ch, u32 n, const LzExtendParams& P, const LzLutParams& Q);
+// settle_kernels.hip (n: the hits of the chunk)
+int lzk_partition(LzCtx& c, bool tagged, u64 n);     // c.keys + c.summ (or tagged records in c.keys) -> records, in place; c.hist, c.run_addr
+int lzk_hist_scan(LzCtx& c, u64 n);                  // after the partition of the chunk: c.hist, c.hist_part, c.bin_base
+int lzk_settle(LzCtx& c, const LzExtendParams& P, u64 n, u32 out_cap);   // -> c.diag_end, c.hsp_out / c.hsp_count, c.dev_counters
+int lzk_hsp_match_counts(LzCtx& c, u32 n_rec, const SeqSlot& q);         // -> c.hsp_mc

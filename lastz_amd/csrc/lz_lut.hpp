@@ -50,7 +50,7 @@ struct LzLutParams {
     const u8* t2; const u8* q2;                   // Gray 2-bit codes: base i at bits 2*((i+PAD2)&3) of byte (i+PAD2)>>2
     const u8* tsp; const u8* qsp;                 // special masks: base i at bit (i+PAD2)&7 of byte (i+PAD2)>>3
     const u8* t2x; const u8* tspx;                // the target's two arrays once more, in 64-byte blocks that overlap by half
-                                                  // (block k = bytes [32k, 32k+64) of the plain array; seed_kernels.hip::lz_scan_fetch)
+                                                  // (block k = bytes [32k, 32k+64) of the plain array; scan_kernels.hip::lz_scan_fetch)
     const u8* tcode; const u8* qcode;             // the code bytes (lz_common.hpp): a special base met by a scan is scored from its class
     s32 xdrop;
 };
@@ -311,7 +311,7 @@ LZ_HD u64 lz_hit_record_tagged(u64 key, u32 summ) { return lz_hit_record(key, su
 
 // ---- wctx: the target context of a table entry (k_scan_hits2).  Both first windows of a hit lie in the 32 bytes of the
 // plain 2-bit array that start at byte bl(pos1) -- the left window is bytes [bl, bl + 16), the right one starts at byte
-// br = bl + 15 or bl + 16 (lz_scan_fetch in seed_kernels.hip reads the same bytes from the half-overlapping blocks) --
+// br = bl + 15 or bl + 16 (lz_scan_fetch in scan_kernels.hip reads the same bytes from the half-overlapping blocks) --
 // and depend on pos1 alone: entry e of wctx holds those 32 bytes for pos1 = wpos[e].
 #define LZ_WCTX_BYTES 32
 struct alignas(16) LzWctx { u32 w[LZ_WCTX_BYTES / 4]; };

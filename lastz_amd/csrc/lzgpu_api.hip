@@ -20,7 +20,7 @@
 // ------------------------------------------------------------------------------ context
 
 static LzCtx g_ctx;
-void lz_phase_clocks_print();                                 // seed_kernels.hip (prints only in a -DLZ_PHASE_CLOCKS build)
+void lz_phase_clocks_print();                                 // settle_kernels.hip (prints only in a -DLZ_PHASE_CLOCKS build)
 LzCtx& lz_ctx() { return g_ctx; }
 
 // The last error message: one per THREAD (B3 may run on a second host thread beside B2, and the problems of a batch run on
@@ -598,8 +598,8 @@ static int ss_count(LzCtx& c, SeedSearch& s)
     LZ_HIP(hipMemsetAsync(c.dev_counters.p, 0, 64, c.stream));                        // [0]=extensions [1]=bp [2]=words
     LZ_HIP(hipMemsetAsync(c.hsp_count.p, 0, 4, c.stream));
 
-    if ((rc = lzk_count_hits(c, s.qs->code_base(), s.lo, s.hi, c.cnt.as<u32>(), c.pk.as<u32>(), c.wiv.as<u32>(), c.wsk.as<u32>(), c.wsv.as<u32>(), c.dev_counters.as<u64>() + 2))) return rc;
-    if ((rc = lzk_scan_counts(c, c.cnt.as<u32>(), c.off.as<u64>(), n))) return rc;
+    if ((rc = lzk_count_hits(c, s.qs->code_base(), s.lo, s.hi))) return rc;
+    if ((rc = lzk_scan_counts(c, n))) return rc;
 
     // total and the sampled prefix sums for the chunk plan come back through pinned memory the device
     // writes itself: one synchronisation, no staged device-to-host copies
@@ -610,7 +610,7 @@ static int ss_count(LzCtx& c, SeedSearch& s)
         LZ_HIP(hipHostMalloc((void**)&c.pinned, ((size_t)ns + 16) * 8, hipHostMallocDefault));
         c.pinned_words = (size_t)ns + 16;
     }
-    if ((rc = lzk_sample_offsets(c, c.off.as<u64>(), c.cnt.as<u32>(), n, LZ_PLAN_STRIDE, ns, c.pinned))) return rc;
+    if ((rc = lzk_sample_offsets(c, n, LZ_PLAN_STRIDE, ns))) return rc;
     c.blk_start_host.assign((size_t)c.blk_count + 1, 0);       // (a chunk's launch of the fill kernel covers its blocks' range of the sorted list)
     LZ_HIP(hipMemcpyAsync(c.blk_start_host.data(), c.blk_start.p, ((size_t)c.blk_count + 1) * 8, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
@@ -712,25 +712,21 @@ static int ss_reserve(LzCtx& c, SeedSearch& s)
 // ranks from the counts that leaves, phase B.  All on c.stream: diagEnd carries from chunk to chunk, in chunk order.
 static int ss_chunk(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
-    const LzExtendParams& P = s.P;
-    u64* keys = c.keys.as<u64>();
-    hipStream_t st = c.stream;
     int rc;
     if (s.fused) {
-        if ((rc = lzk_scan_fused(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, ch.nh, P, s.Q, c.lut.as<LzLutEntry>(), keys, st))) return rc;
+        if ((rc = lzk_scan_fused(c, s.lo, ch, s.n, s.P, s.Q))) return rc;
     } else {
-        if ((rc = lzk_fill_hits(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, keys, st))) return rc;
-        if ((rc = lzk_scan_hits(c, s.mode, P, s.Q, keys, ch.nh, c.score_tab.as<s32>(), c.lut.as<LzLutEntry>(), c.bins.as<u8>(), st))) return rc;
+        if ((rc = lzk_fill_hits(c, s.lo, ch, s.n))) return rc;
+        if ((rc = lzk_scan_hits(c, s.mode, s.P, s.Q, ch.nh))) return rc;
     }
-    if ((rc = lzk_partition(c, s.fused, keys, s.fused ? nullptr : c.summ.as<u32>(), ch.nh, c.hist.as<u32>(), c.run_addr.as<u32>(), st))) return rc;
-    if ((rc = lzk_hist_scan(c, ch.nh, c.hist.as<u32>(), c.hist_part.as<u32>(), c.bin_base.as<u32>(), st))) return rc;
-    return lzk_settle(c, P, keys, ch.nh, c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(), c.diag_end.as<u32>(), c.score_tab.as<s32>(),
-                      c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), s.out_cap, c.dev_counters.as<u64>(), st);
+    if ((rc = lzk_partition(c, s.fused, ch.nh))) return rc;
+    if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
+    return lzk_settle(c, s.P, ch.nh, s.out_cap);
 }
 // ... of a search without extension (process_for_plain_hit): every hit is reported
 static int ss_chunk_plain(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
-    int rc = lzk_fill_hits(c, s.lo, ch.i0, ch.i1, c.wsk.as<u32>(), c.wsv.as<u32>(), s.n, c.off.as<u64>(), ch.base, c.keys.as<u64>(), c.stream); if (rc) return rc;
+    int rc = lzk_fill_hits(c, s.lo, ch, s.n); if (rc) return rc;
     std::vector<u64> hk(ch.nh);
     LZ_HIP(hipMemcpyAsync(hk.data(), c.keys.p, (size_t)ch.nh * 8, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
@@ -751,9 +747,7 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
     const bool gpu_counts = a->extend && n_rec > 0 && n_rec <= s.out_cap;
     if (gpu_counts) {
         if ((rc = c.hsp_mc.ensure((size_t)n_rec * 20))) return rc;
-        if ((rc = lzk_hsp_match_counts(c, c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), n_rec, n_rec,
-                                       c.target.raw_base(), s.qs->raw_base(), c.target.code_base(), s.qs->code_base(),
-                                       c.hsp_mc.as<u32>(), c.stream))) return rc;
+        if ((rc = lzk_hsp_match_counts(c, n_rec, *s.qs))) return rc;
     }
     c.timer.resolve();
     { std::lock_guard<std::mutex> lk(c.counters_m);

@@ -3,7 +3,7 @@ per table entry) and its tagged hit record, on the CPU.
 
 For every end position pos1 of a short target -- both sequence ends, all four phases of pos1 inside a byte -- the two
 16-byte windows that lz_wctx_windows takes from the entry lz_wctx_make built must be the windows lz_scan_fetch
-(seed_kernels.hip) takes from the half-overlapping blocks, restated here in numpy over the same arrays.  And the tagged
+(scan_kernels.hip) takes from the half-overlapping blocks, restated here in numpy over the same arrays.  And the tagged
 record with its tag cleared must be lz_hit_record(key, summ), for SLOW and other summaries, the tag being bits 8..15
 of the diagonal.  CPU only."""
 import ctypes as C

@@ -16,7 +16,7 @@ import pytest
 import helpers as H
 
 TILE = 16384                                                 # lz_tile_runs.hpp: LZ_PP_TILE_HOST
-WINDOW, SORTW = 448, 12                                      # seed_kernels.hip: 64 * LZ_S2_ROUNDS, LZ_S2_SORTW
+WINDOW, SORTW = 448, 12                                      # settle_kernels.hip: 64 * LZ_S2_ROUNDS, LZ_S2_SORTW
 S2_TILE = WINDOW * SORTW                                     # LZ_S2_TILE = 5376
 BLOCK = 128                                                  # lz_tile_runs.hpp: LZ_TR_BLOCK (a block covers BLOCK - 1 tiles)
 U8P = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
