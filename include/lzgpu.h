@@ -103,6 +103,13 @@ int lzgpu_table_prepare(const uint8_t* t, uint32_t tlen, uint32_t start, uint32_
  * postable.prev[1+(end-adjStart)/step], src/pos_table.h:126-165) so that host code which reads
  * the table (capsule writer, --tableonly, masking) keeps working.  Either pointer may be NULL. */
 int lzgpu_table_export(uint32_t* last, uint32_t* prev);
+/* Overwrite n single bytes of the resident target, on the device and in the library's host copy: t[pos[k]] = bytes[k].
+ * For the "fences" lastz sets around a chore's target interval while it searches (fence_sequence_interval,
+ * src/sequences.c:7789-7828: the bytes at s - 1 and e become NUL, which ends every extension there) and takes away
+ * afterwards.  The position table is NOT rebuilt: the caller answers for the words over the patched bytes (a chore's
+ * fences lie outside the interval its position filter admits).  The target's encodings are redone by the next search or
+ * gapped call, a pass over the target each.  LZGPU_ERR_ARG for a position past the end (nothing is written then). */
+int lzgpu_target_patch(const uint32_t* pos, const uint8_t* bytes, uint32_t n);
 /* Rebuild the table from the target bytes already resident in HBM (same geometry as the last
  * lzgpu_table_prepare); used to time B1 without the host->device copy. */
 int lzgpu_table_rebuild(void);
@@ -190,6 +197,24 @@ typedef struct lz_self_args {
     uint32_t        n_sep2;
 } lz_self_args;
 int lzgpu_seed_hit_search_self(const lz_search_args* args, const lz_self_args* self, lz_hsp** out, uint64_t* n_out);
+
+/* ---- B2 under a position filter (lastz --chores) ------------------------------------------------
+ * seed_hit_search with hp->posFilter set (src/lastz.c:1503-1512): every raw hit whose window is not wholly inside
+ * both intervals is dropped before it is processed (filter_seed_hit_by_pos, src/seed_search.c:2269-2310, called at
+ * :1072-1074); everything else -- discovery order, chunking, entropy, threshold -- is what lzgpu_seed_hit_search does
+ * with the hits that remain.  The X-drop extension is NOT limited by the intervals: the reference filters the seed, not
+ * the HSP.  The query interval is intersected with the search interval [start, end) of the arguments.  An empty window
+ * or intersection returns 0 with no HSPs; interval ends beyond the sequences are clamped; t_start > t_end or
+ * q_start > q_end returns LZGPU_ERR_ARG; bucket owners (lzgpu_set_bucket_owner) return LZGPU_NH_UNSUPPORTED before any
+ * work is done.  Not combined with a self-comparison.  Counters: see lz_counters.
+ * (lastz --chores also fences both sequences for the time of the search, src/lastz.c:3028-3032: the caller hands the
+ * query in with its fences and puts the target's on the device with lzgpu_target_patch.)
+ *
+ * hp->targetInterval / hp->queryInterval exactly as filter_seed_hit_by_pos reads them (src/seed_search.c:2269-2310):
+ * a raw hit with window [pos - L, pos) in each sequence is kept iff
+ *   t_start <= pos1 - L && pos1 <= t_end && q_start <= pos2 - L && pos2 <= q_end */
+typedef struct lz_pos_filter { uint32_t t_start, t_end, q_start, q_end; } lz_pos_filter;
+int lzgpu_seed_hit_search_within(const lz_search_args* args, const lz_pos_filter* within, lz_hsp** out, uint64_t* n_out);
 
 /* ---- B1 + B2 for many small rectangles of the two sequences at once ----------------------------
  * What src/tweener.c:769-829 (bounded_align) does for every in-between window of `lastz --inner=<score>`:
@@ -324,6 +349,10 @@ int lzgpu_reduce_to_chain(const lz_chain_args* a, const lz_segment* segs, uint32
 int lzgpu_reduce_to_chain_batch(const lz_chain_args* a, const lz_segment* const* segs, const uint32_t* n, uint32_t k,
                                 uint32_t** kept, uint32_t* n_kept, int32_t* best);
 
+/* Under a position filter (lzgpu_seed_hit_search_within) the counters are those of the restricted search: words counts
+ * the query words inside the intersected interval and raw_hits the hits that survive the filter.  The reference's
+ * collect_stats build counts both before the processor filters, so these two differ from it there (extensions,
+ * bp_extended and hsps do not); counting its way would take a second pass over the whole query per chore. */
 typedef struct lz_counters {       /* same events as the reference's collect_stats build          */
     uint64_t words;                /* "words in seq 2"    src/seed_search.c:514                   */
     uint64_t raw_hits;             /* "raw seed hits"     src/seed_search.c:865                   */

@@ -556,7 +556,7 @@ u64 seed_hit_search
 
 	if ((pt != devTable) || (devTable == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
 	 || (processor != process_for_simple_hit) || (hp->gfExtend != gfexXDrop)
-	 || (hp->hspThreshold.t != 'S') || (hp->posFilter) || (hp->minMatches >= 0) || (hp->reportEntropy)
+	 || (hp->hspThreshold.t != 'S') || ((hp->posFilter) && (selfCompare)) || (hp->minMatches >= 0) || (hp->reportEntropy)
 	 || ((!selfCompare) && (bandWidth != 0)) || (searchLimit != 0)
 	 || (seq2->fileType == seq_type_qdna) || (hp->seq1 != seq1) || (hp->seq2 != seq2)
 	 || (memcmp (upperCharToBits, devCharToBits, 256) != 0)
@@ -585,6 +585,30 @@ u64 seed_hit_search
 		else rc = lzgpu_seed_hit_search_self (&a, &sa, &h, &n);
 		free (sep1);  free (sep2);
 		if (rc < 0) suicidef ("lzgpu_seed_hit_search_self: %s", lzgpu_last_error());
+		}
+	else if (hp->posFilter)                                     /* --chores: the seed hits inside the chore's intervals (src/lastz.c:1503-1512, 1627), dropped on the device */
+		{
+		lz_pos_filter pf;
+		uint32_t      fPos[2];
+		uint8_t       fNow[2], fWas[2];
+		uint32_t      nf = 0;
+		pf.t_start = hp->targetInterval.s;  pf.t_end = hp->targetInterval.e;
+		pf.q_start = hp->queryInterval.s;   pf.q_end = hp->queryInterval.e;
+		/* lastz has fenced both sequences for this search (src/lastz.c:3028-3032): the query goes to the device with
+		 * its fences, the target's are put on the device's copy and taken away again */
+		if ((seq1->hasLeftFence) && (seq1->leftFencePos < seq1->len))
+			{ fPos[nf] = seq1->leftFencePos;   fNow[nf] = seq1->v[seq1->leftFencePos];   fWas[nf++] = seq1->leftFenceCh; }
+		if ((seq1->hasRightFence) && (seq1->rightFencePos < seq1->len))
+			{ fPos[nf] = seq1->rightFencePos;  fNow[nf] = seq1->v[seq1->rightFencePos];  fWas[nf++] = seq1->rightFenceCh; }
+		rc = lzgpu_target_patch (fPos, fNow, nf);
+		if (rc == 0)
+			{
+			int rc2;
+			rc  = lzgpu_seed_hit_search_within (&a, &pf, &h, &n);
+			rc2 = lzgpu_target_patch (fPos, fWas, nf);
+			if ((rc >= 0) && (rc2 != 0)) rc = rc2;
+			}
+		if (rc < 0) suicidef ("lzgpu_seed_hit_search_within: %s", lzgpu_last_error());
 		}
 	else
 		{

@@ -99,7 +99,7 @@ k_count_sorted_owned(const u32* __restrict__ sk, const u32* __restrict__ sv, u32
 // self-comparison (lz_common.hpp, LzSelfDev): only the hits in [lo, hi) of pos1 count, and every list is clipped to them
 // with two binary searches over its (descending) positions -- so, unlike k_count_sorted, the positions are read.  The 16
 // probes of a group go through their searches in lock step (lz_clip_runs): their bounds and then each step's 16 loads are
-// in flight together.
+// in flight together.  A position filter (LZ_SELF_WINDOW, lzgpu_seed_hit_search_within) is the same clip with constant bounds.
 #define LZ_SELF_GROUP 16
 __global__ void __launch_bounds__(LZ_TPB)
 k_count_sorted_self(const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, u32 lo, LzSeedDev sd,
@@ -293,7 +293,8 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 #define LZ_F2_CAP   2560                             // k_fill_hits2's CAP: own[] 5 KiB + 4.5 KiB of tables per wave = four workgroups per CU (the 64 positions of a wave have 2.5 k hits on the 50 Mbp pair)
 #define LZ_F2_WORDS (LZ_F2_CAP / 2 / 64)             // 32-bit words of own[] per lane
 // SELF: a self-comparison (lz_common.hpp, LzSelfDev): step 1 clips every list to the hits that survive, before the
-// wave scan (k_count_sorted_self counted the same); the rest of the kernel is the same code.
+// wave scan (k_count_sorted_self counted the same); the rest of the kernel is the same code.  Also the instantiation of a
+// position filter (LZ_SELF_WINDOW): lz_self_bounds gives its constant window.
 template <bool SELF>
 __global__ void __launch_bounds__(LZ_TPB)
 k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
@@ -416,7 +417,7 @@ int lzk_fill_hits(LzCtx& c, u32 lo, const LzChunk& ch, u32 n)
     const u64* const off = c.off.as<u64>(); u64* const keys = c.keys.as<u64>();
     const dim3 grid((unsigned)(((u64)n + LZ_TPB - 1) / LZ_TPB));
     c.timer.begin("k_fill_hits", c.stream);
-    if (c.self.mode != LZ_SELF_OFF)                             // (lzgpu_seed_hit_search_self declines bucket owners: only k_fill_hits2 clips)
+    if (c.self.mode != LZ_SELF_OFF)                             // (lzgpu_seed_hit_search_self / _within decline bucket owners: only k_fill_hits2 clips)
         hipLaunchKernelGGL(k_fill_hits2<true>, grid, dim3(LZ_TPB), 0, c.stream,
                            lo, ch.i0, ch.i1, c.seed, c.wstart.as<u32>(), c.wpos.as<u32>(), sk, sv, n, off, ch.base, keys, c.self);
     else if (c.n_owners > 1)

@@ -120,11 +120,18 @@ LZ_HD void lz_fill_hits_at(const u8* qcode, u32 pos2, const LzSeedDev& sd, const
 #define LZ_SELF_SAME      1           // same strand, optional band
 #define LZ_SELF_OPP       2           // opposite strands, seq2 unpartitioned
 #define LZ_SELF_OPP_PARTS 3           // opposite strands, [multi]
+// ---- position filter (lastz --chores: hp->posFilter, filter_seed_hit_by_pos, src/seed_search.c:2269-2310): not a
+// self-comparison, but the same shape -- the hits kept are those with pos1 in the constant window [wlo, whi), whatever
+// pos2 is (the query half of the filter is the search interval, intersected on the host: lzgpu_seed_hit_search_within)
+#define LZ_SELF_WINDOW    4
 struct LzSelfDev {
     u32 mode, L, len2, band;
     const u32* sep1; u32 n_sep1;
-    const u32* sep2; u32 n_sep2;
+    u32 wlo;                          // LZ_SELF_WINDOW: the hit END positions kept are [wlo, whi), wlo >= L > 0
+    const u32* sep2; u32 n_sep2;      // (wlo / whi sit where the pointers' alignment left holes: the struct, a kernel
+    u32 whi;                          // argument of the unclipped instantiations too, keeps its size)
 };
+static_assert(sizeof(LzSelfDev) == 48, "LzSelfDev is a kernel argument: keep its size");
 
 // number of separators <= x (the partition of a non-separator position x is this minus one)
 LZ_HD u32 lz_sep_rank(const u32* sep, u32 n, u32 x)
@@ -151,9 +158,22 @@ LZ_HD void lz_self_bounds(const LzSelfDev& s, u32 pos2, u32& lo, u32& hi)
         const u32 thr = s.sep2[ix] + s.sep2[ix + 1] - q;
         const u32 a = s.sep1[ix], b = s.sep1[ix + 1];
         hi = (thr < a ? a : thr > b ? b : thr) + s.L;
+    } else if (s.mode == LZ_SELF_WINDOW) {                      // :2304: pos1 - L >= tStart, pos1 <= tEnd
+        lo = s.wlo; hi = s.whi;
     } else {
         hi = 0xFFFFFFFFu;
     }
+}
+
+// The clip of a position filter whose target interval is [t_start, t_end) (filter_seed_hit_by_pos: a hit ending at pos1
+// is kept iff t_start <= pos1 - L and pos1 <= t_end); an end beyond the sequence is clamped.  false: no hit can survive.
+LZ_HD bool lz_window_self(u32 t_start, u32 t_end, u32 L, u32 tlen, LzSelfDev& s)
+{
+    const u64 wlo = (u64)t_start + L, whi = (u64)(t_end < tlen ? t_end : tlen) + 1u;
+    s = LzSelfDev{};
+    if (whi <= wlo) return false;
+    s.mode = LZ_SELF_WINDOW; s.L = L; s.wlo = (u32)wlo; s.whi = (u32)whi;
+    return true;
 }
 
 // Shrink the list wpos[a, a + len) (descending positions) to the entries in [lo, hi): two searches, for the number of

@@ -127,7 +127,7 @@ struct LzCtx {
     // 7 launches, 0.73 s at 2048; 5 launches, 0.48 s at 8192 and beyond).  Default: 1/32 of the anchors, within [2048, 16384].
     u32 dp_window = 0;                // 0: the default rule; lzgpu_set_dp_window fixes it (LZGPU_DP_WINDOW, for one call, goes before either)
     u32 n_owners = 1, owner = 0;      // bucket ownership (lzgpu_set_bucket_owner)
-    LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self); mode LZ_SELF_OFF otherwise
+    LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self) or its position filter (lzgpu_seed_hit_search_within); mode LZ_SELF_OFF otherwise
     DevBuf self_sep;                  // its separators on the device: sep1, then sep2
     std::vector<u64> last_order;      // two sort words per HSP of the last search
     int min_scan_mode = 0;            // lzgpu_set_scan_mode

@@ -353,6 +353,27 @@ extern "C" int lzgpu_target_upload(const uint8_t* t, uint32_t tlen)
     return slot_upload(c, c.target, t, tlen, true);
 }
 
+// A few bytes of the resident target overwritten in place (the fences lastz puts around a chore's target interval,
+// src/sequences.c:7789-7828, and their removal).  The position table is left as it is; every encoding of the target is
+// made again by the next call that needs it, and so is wctx.
+extern "C" int lzgpu_target_patch(const uint32_t* pos, const uint8_t* bytes, uint32_t n)
+{
+    int rc = require_init(); if (rc) return rc;
+    LzCtx& c = g_ctx;
+    if (n && (!pos || !bytes)) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    if (!c.target.have_raw || c.target.host.size() != c.target.len) return lz_fail(LZGPU_ERR_STATE, "no target on the device");
+    for (u32 k = 0; k < n; k++) if (pos[k] >= c.target.len) return lz_fail(LZGPU_ERR_ARG, "target position %u is past the end (%u)", pos[k], c.target.len);
+    if (!n) return 0;
+    for (u32 k = 0; k < n; k++) {
+        c.target.host[pos[k]] = bytes[k];
+        LZ_HIP(hipMemcpyAsync(c.target.raw_base() + pos[k], &c.target.host[pos[k]], 1, hipMemcpyHostToDevice, c.stream));
+    }
+    LZ_HIP(hipStreamSynchronize(c.stream));
+    c.target.code_key = 0; c.target.dp_key = 0;
+    c.wctx_gen = 0; c.wctx_code_key = 0;
+    return 0;
+}
+
 extern "C" int lzgpu_table_rebuild(void)
 {
     LzCtx& c = g_ctx;
@@ -835,6 +856,35 @@ extern "C" int lzgpu_seed_hit_search_self(const lz_search_args* a, const lz_self
     }
     c.self = sd;
     rc = seed_search(a, out, n_out);
+    c.self = LzSelfDev{};
+    return rc;
+}
+
+// Position filter (lastz --chores: hp->posFilter, filter_seed_hit_by_pos, src/seed_search.c:2269-2310, the first thing
+// the hit processor does, :1072-1074).  A raw hit is kept iff its window lies inside both intervals.  The query half is
+// the search interval intersected with [q_start, q_end); the target half is a constant window of hit end positions,
+// [t_start + L, t_end + 1) (lz_window_self), to which the kernels that clip for a self-comparison clip every list (LZ_SELF_WINDOW).  The
+// extension is not limited: the reference filters the seed, not the HSP.
+extern "C" int lzgpu_seed_hit_search_within(const lz_search_args* a, const lz_pos_filter* w, lz_hsp** out, uint64_t* n_out)
+{
+    int rc = search_enter(a && w && out && n_out && a->sub, out, n_out); if (rc) return rc;
+    LzCtx& c = g_ctx;
+    if (w->t_start > w->t_end || w->q_start > w->q_end)
+        return lz_fail(LZGPU_ERR_ARG, "position filter: an interval ends before it starts (target %u-%u, query %u-%u)", w->t_start, w->t_end, w->q_start, w->q_end);
+    if (c.n_owners > 1) return LZGPU_NH_UNSUPPORTED;             // (the owner path has no clip)
+    SeqSlot* qs; u32 qlen;                                      // (the length only: seed_search uploads a host-pointer query)
+    if ((rc = lz_search_query(c, a->query, a->qlen, a->query_slot, false, qs, qlen))) return rc;
+    // the search interval as ss_query reads it, then its intersection with the query interval
+    const u32 lo = a->start, hi = a->end ? a->end : qlen;
+    if (hi <= lo) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval is void (%u-%u)", lo, hi);
+    if (hi > qlen) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search(), interval end is bad (%u>%u)", hi, qlen);
+    lz_search_args b = *a;
+    b.start = std::max(lo, w->q_start); b.end = std::min(hi, w->q_end);
+    const u32 L = (u32)c.seed.length;
+    LzSelfDev sd;
+    if (b.end <= b.start || b.end - b.start < L || !lz_window_self(w->t_start, w->t_end, L, c.geom.tlen, sd)) return 0;   // no window fits: no hits, no HSPs
+    c.self = sd;
+    rc = seed_search(&b, out, n_out);
     c.self = LzSelfDev{};
     return rc;
 }

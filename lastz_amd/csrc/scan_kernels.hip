@@ -446,7 +446,7 @@ k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 // LDS: the tables + a wave's own[] of CAP cells and 4.5 KiB of lists: 8 waves x 2560 cells, 12 x 1024 or 16 x 512 in 160 KiB.
 // The kernel is bound by the latency of the scans' dependent table look-ups, which only other waves hide: 84.5, 67.9, 61.6 ms per
 // step on the 50 Mbp pair with 8, 12, 16 waves (121 VGPRs: four waves per SIMD), however short the pieces get.  A
-// self-comparison's clipping needs 177 registers: it runs with 8 waves.
+// self-comparison's clipping needs 177 registers: it runs with 8 waves (and so does a position filter, the same instantiation).
 static u32 lz_fused_tpb(LzCtx& c)
 {
     return c.self.mode != LZ_SELF_OFF ? 512u : 1024u;

@@ -56,6 +56,10 @@ class SelfArgs(C.Structure):
                 ("sep2", C.c_void_p), ("n_sep2", C.c_uint32)]
 
 
+class PosFilter(C.Structure):
+    _fields_ = [("t_start", C.c_uint32), ("t_end", C.c_uint32), ("q_start", C.c_uint32), ("q_end", C.c_uint32)]
+
+
 class Counters(C.Structure):
     _fields_ = [("words", C.c_uint64), ("raw_hits", C.c_uint64), ("extensions", C.c_uint64),
                 ("bp_extended", C.c_uint64), ("hsps", C.c_uint64), ("dp_cells", C.c_uint64),
@@ -70,9 +74,9 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 
 # every symbol include/lzgpu.h declares (tests check that the library exports all of them)
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
-           "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_table_num_words",
+           "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_table_num_words",
            "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_device_copy",
-           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
+           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
            "lzgpu_set_bucket_owner", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
@@ -106,6 +110,7 @@ class Lib:
         f("seed_hit_search").argtypes = [C.POINTER(SearchArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         if prefix == "lzgpu_":
             self.L.lzgpu_seed_hit_search_self.argtypes = [C.POINTER(SearchArgs), C.POINTER(SelfArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+            self.L.lzgpu_seed_hit_search_within.argtypes = [C.POINTER(SearchArgs), C.POINTER(PosFilter), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         f("table_prepare").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(SeedDesc), C.c_uint32]
         f("set_hit_capacity").argtypes = [C.c_uint64]
@@ -174,6 +179,14 @@ class Lib:
                     "lzgpu_table_prepare")
         self._weight = sd.weight_bits
 
+    def target_patch(self, pos, values):
+        """t[pos[k]] = values[k] in the resident target (a chore's fences); the table stays as it is"""
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        values = np.ascontiguousarray(values, dtype=np.uint8)
+        assert len(pos) == len(values)
+        self.L.lzgpu_target_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._check(self.L.lzgpu_target_patch(_ptr(pos), _ptr(values), len(pos)), "lzgpu_target_patch")
+
     def table_rebuild(self):
         self._check(self.L.lzgpu_table_rebuild(), "lzgpu_table_rebuild")
 
@@ -228,6 +241,13 @@ class Lib:
         s.sep2, s.n_sep2 = (_ptr(seps[1]) if len(seps[1]) else None), len(seps[1])
         return self._search(s, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end)
 
+    def seed_hit_search_within(self, sub, t_interval, q_interval, q=None, slot=-1, xdrop=910, hsp_threshold=3000, entropic=True,
+                               extend=True, start=0, end=0):
+        """lastz --chores: only the seed hits whose windows lie inside t_interval = (start, end) of the target and
+        q_interval of the query (hp->targetInterval / hp->queryInterval, origin-0 half-open); the extension is not limited"""
+        w = PosFilter(t_interval[0], t_interval[1], q_interval[0], q_interval[1])
+        return self._search(w, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end)
+
     def _search(self, self_args, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end):
         a = SearchArgs()
         sub = np.ascontiguousarray(sub, dtype=np.int32)
@@ -243,6 +263,9 @@ class Lib:
         n = C.c_uint64()
         if self_args is None:
             self._check(self._f("seed_hit_search")(C.byref(a), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search")
+        elif isinstance(self_args, PosFilter):
+            self._check(self.L.lzgpu_seed_hit_search_within(C.byref(a), C.byref(self_args), C.byref(out), C.byref(n)),
+                        "lzgpu_seed_hit_search_within")
         else:
             self._check(self.L.lzgpu_seed_hit_search_self(C.byref(a), C.byref(self_args), C.byref(out), C.byref(n)),
                         "lzgpu_seed_hit_search_self")
