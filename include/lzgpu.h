@@ -146,6 +146,26 @@ int lzgpu_table_share(int rank, int world, const char* dir);
  * table of this version, LZGPU_ERR_STATE for a damaged one. */
 int lzgpu_table_save(const char* path);
 int lzgpu_table_load(const char* path);
+/* ---- the word-count limit (lastz --maxwordcount=<n> and =<p>%) ---------------------------------
+ * limit_position_table(pt, limit, 0) (src/pos_table.c:1763-1948, called after every table build at src/lastz.c:1219-1221;
+ * maxChasm / step == 0): a word whose list holds more than `limit` positions loses its whole list, every other list
+ * keeps its content and its order.  From now on every search (lzgpu_seed_hit_search, _self, _within, with or without
+ * bucket owners) sees the table without those words; lzgpu_table_num_words() counts the entries they see.  limit == 0
+ * lifts the limit; a different limit starts from the unlimited table again; the same limit is a no-op.  The unlimited
+ * table stays resident: lzgpu_table_export, _geom, _buffers, _save and _share keep describing it, and every call that
+ * makes a table (lzgpu_table_prepare, _rebuild, _load, _adopt + _commit) ends the limit.  A limit that removes every word
+ * leaves a valid empty table: searches return no HSPs.  lzgpu_window_search builds its own tables and is not affected
+ * (nor are the tweener's in the reference).  Costs 4 (2^weight + 1) bytes + 4 bytes per entry kept while in force.
+ * LZGPU_ERR_STATE without a table. */
+int lzgpu_table_limit(uint32_t limit);
+/* find_position_table_limit(pt, keep) (src/pos_table.c:2000-2034, called at src/lastz.c:1215-1218) on the resident
+ * UNLIMITED table: the smallest list length such that the words up to it hold at least the fraction `keep` of the
+ * positions, in the reference's arithmetic (u32 sums and products, the float product numPositions * keep, ceil in
+ * double); 0 -- lastz then sets no limit -- where no length qualifies.  LZGPU_ERR_STATE without a table. */
+int lzgpu_table_find_limit(float keep, uint32_t* limit);
+/* position_table_count_distribution (src/pos_table.c:2064-2140) of the unlimited table: the distinct list lengths > 0 in
+ * increasing order and the number of words that have each.  Both arrays are released with lzgpu_free(). */
+int lzgpu_table_count_distribution(uint32_t** count, uint32_t** words, uint32_t* n);
 /* device-to-device copy on the library's stream (lets a caller that received the broadcast in
  * its own allocation hand it over without knowing which HIP runtime object owns the stream). */
 int lzgpu_device_copy(void* dst_dev, const void* src_dev, uint64_t bytes);

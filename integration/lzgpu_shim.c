@@ -65,6 +65,7 @@ alignel*  ref_tweener_interpolate (alignel* a, seq* seq1, seq* seq2, int selfCom
 /* which host objects the device copy currently mirrors */
 static postable* devTable   = NULL;
 static int       devTableOnHost = false;                   /* devTable->last / ->prev hold the table (lzgpu_table_export ran) */
+static u32       devLimit   = 0;                            /* the word-count limit in force on the device's table (lzgpu_table_limit), 0: none */
 static u8*       devTargetV = NULL;
 static unspos    devTargetLen = 0;
 static s8        devCharToBits[256];
@@ -159,7 +160,7 @@ __attribute__((constructor)) static void early_device_start (int argc, char** ar
 	if (files >= 2) lzgpu_init_async (-1);
 	}
 
-static void drop_device_table (void) { devTable = NULL;  devTargetV = NULL;  devTargetLen = 0;  devTableOnHost = false; }
+static void drop_device_table (void) { devTable = NULL;  devTargetV = NULL;  devTargetLen = 0;  devTableOnHost = false;  devLimit = 0; }
 
 /* The host copy in the reference's layout (last[] / prev[]) costs a device-to-host copy of 64 MiB + 4 bytes per
  * target base; the search and the gapped stage never read it.  It is made on demand: before any reference routine
@@ -171,6 +172,9 @@ static void host_table_needed (postable* pt)
 	rc = lzgpu_table_export (pt->last, pt->prev);
 	if (rc != 0) suicidef ("lzgpu_table_export: %s", lzgpu_last_error());
 	devTableOnHost = true;
+	/* the export is the table as it was built: under a word-count limit the reference's own routine takes the same lists
+	   away, and leaves in last[] / prev[] of the removed words what it always leaves there */
+	if (devLimit != 0) ref_limit_position_table (pt, devLimit, 0);
 	note ("table", "copied to the host for a reference routine");
 	}
 
@@ -480,8 +484,27 @@ void mask_seed_position_table
 	ref_mask_seed_position_table (pt, seq, start, end, upperCharToBits, hitSeed);
 	}
 
+/* --maxwordcount=<n> (src/lastz.c:1219-1221): without a chasm the limit removes whole lists, which the library does on a copy
+   of the device's table (lzgpu_table_limit) -- the searches stay on the GPU.  The chasm form protects single positions of the
+   removed lists (src/pos_table.c:1784-1832, 1924-1940), a multi-process run shares the unlimited table between its ranks and
+   the discard dump walks the host copy: those take the reference's routine, and the device's table is dropped, as before. */
 void limit_position_table (postable* pt, u32 limit, unspos maxChasm)
-	{ host_table_needed (pt);  if (pt == devTable) drop_device_table ();  ref_limit_position_table (pt, limit, maxChasm); }
+	{
+	int rc;
+	multi_init ();
+	if ((pt != NULL) && (pt == devTable) && (maxChasm / pt->step == 0) && (mgWorld == 1) && (!pos_table_dbgShowDiscards)
+	 && (devLimit == 0))                                         /* (a second limit works on what the first left: not the library's contract) */
+		{
+		rc = lzgpu_table_limit (limit);
+		if (rc != 0) suicidef ("lzgpu_table_limit: %s", lzgpu_last_error());
+		devLimit = limit;
+		if (devTableOnHost) ref_limit_position_table (pt, limit, maxChasm);    /* (the host copy follows) */
+		note ("limit", "done on the GPU");
+		return;
+		}
+	note ("limit", "reference path");
+	host_table_needed (pt);  if (pt == devTable) drop_device_table ();  ref_limit_position_table (pt, limit, maxChasm);
+	}
 
 void dump_position_table (FILE* f, postable* pt, seed* hitSeed, int showPositions, int showCounts)
 	{ host_table_needed (pt);  ref_dump_position_table (f, pt, hitSeed, showPositions, showCounts); }
@@ -492,8 +515,22 @@ unspos count_position_table (postable* pt)
 poscount* position_table_count_distribution (postable* pt)
 	{ host_table_needed (pt);  return ref_position_table_count_distribution (pt); }
 
+/* --maxwordcount=<p>% (src/lastz.c:1215-1218): the lists' lengths are sorted and counted on the device, and the reference's
+   arithmetic is applied to the few thousand (length, words) pairs; a table that is on the host already, a limited one or a
+   multi-process run take the reference's walk */
 u32 find_position_table_limit (postable* pt, float keep)
-	{ host_table_needed (pt);  return ref_find_position_table_limit (pt, keep); }
+	{
+	multi_init ();
+	if ((pt != NULL) && (pt == devTable) && (!devTableOnHost) && (devLimit == 0) && (mgWorld == 1))
+		{
+		uint32_t limit = 0;
+		int rc = lzgpu_table_find_limit (keep, &limit);
+		if (rc != 0) suicidef ("lzgpu_table_find_limit: %s", lzgpu_last_error());
+		note ("limit", "found on the GPU");
+		return limit;
+		}
+	host_table_needed (pt);  return ref_find_position_table_limit (pt, keep);
+	}
 
 u64 write_capsule_file (FILE* f, char* filename, seq* seq, u8* revNucs, postable* pt, seed* seed)
 	{ host_table_needed (pt);  return ref_write_capsule_file (f, filename, seq, revNucs, pt, seed); }

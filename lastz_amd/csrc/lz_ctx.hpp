@@ -75,7 +75,17 @@ struct LzCtx {
     LzSeedDev seed;
     DevBuf wstart, wpos;            // CSR table
     u64 num_words = 0;
-    u64 table_gen = 0;              // counts the changes of wpos (table build, adopt, commit)
+    u64 table_gen = 0;              // counts the changes of wpos (table build, adopt, commit, a word-count limit set or lifted)
+    // a word-count limit in force (lzgpu_table_limit, limit_kernels.hip): wstart / wpos / num_words above are the LIMITED table the
+    // searches read, and the table as it was built stands aside here; without a limit these are empty
+    u32 limit = 0;                  // 0: none
+    DevBuf full_wstart, full_wpos;
+    u64 full_num_words = 0;
+    bool limited() const { return full_wstart.p != nullptr; }    // (a limit that removes nothing keeps the table as it is: limit != 0, not limited())
+    // the table as it was built, which export / geom / buffers / save / share describe whatever the searches see
+    const DevBuf& built_wstart() const { return limited() ? full_wstart : wstart; }
+    const DevBuf& built_wpos() const { return limited() ? full_wpos : wpos; }
+    u64 built_num_words() const { return limited() ? full_num_words : num_words; }
     DevBuf wctx;                    // derived, like two_x: 32 bytes of the target's 2-bit codes per table entry (lz_lut.hpp; read by k_scan_hits2)
     u64 wctx_gen = 0; uint64_t wctx_code_key = 0;   // the table generation and the target codes wctx was built from (0: not built)
 
@@ -144,7 +154,7 @@ struct LzCtx {
     // describes their contents -- nothing outlives the device context it was made on
     void release_device_memory()
     {
-        DevBuf* all[] = { &wstart, &wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
+        DevBuf* all[] = { &wstart, &wpos, &full_wstart, &full_wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
                           &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab,
                           &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep,
                           &dp.jobs, &dp.ids, &dp.res, &dp.tab, &dp.tb, &dp.rows, &dp.ops, &dp.ops_off, &dp.ops_out, &dp.pieces, &dp.rings, &dp.sel_jobs, &dp.sel_res, &dp.problems,
@@ -155,7 +165,7 @@ struct LzCtx {
         queries.clear();
         if (pinned) (void)hipHostFree(pinned);
         pinned = nullptr; pinned_words = 0;
-        have_table = false; wctx_gen = 0; wctx_code_key = 0;
+        have_table = false; wctx_gen = 0; wctx_code_key = 0; limit = 0; full_num_words = 0;
         score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
         win_attr_set = false; settle_attr_set = false;
     }
@@ -180,6 +190,10 @@ int lzk_overlap32(LzCtx& c, const u8* src, u8* dst, size_t nblocks);
 int lzk_table_build(LzCtx& c);
 int lzk_table_export(LzCtx& c, u32* last_dev, u32* prev_dev, u32 prev_entries);
 int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.wpos and c.target.two
+// limit_kernels.hip (these synchronise c.stream)
+void lz_limit_lift(LzCtx& c);       // c.wstart / c.wpos / c.num_words are the table as it was built again; the limited copy is released
+int lzk_table_limit(LzCtx& c, u32 limit);                        // c.wstart / c.wpos -> the copy without the words of more than `limit` entries, put in their place
+int lzk_table_count_distribution(LzCtx& c, std::vector<u32>& count, std::vector<u32>& words);   // the distinct list lengths > 0, ascending, and the words that have each
 // enum_kernels.hip (the query positions [lo, hi), n = hi - lo of them: c.cnt, c.off, c.pk, c.wiv, c.wsk, c.wsv, sized by the caller)
 int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi);   // honours c.n_owners / c.owner and c.self
 int lzk_scan_counts(LzCtx& c, u32 n);

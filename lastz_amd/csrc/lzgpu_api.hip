@@ -329,6 +329,7 @@ extern "C" int lzgpu_table_prepare(const uint8_t* t, uint32_t tlen, uint32_t sta
     if ((rc = lzh_seed_to_dev(seed, c.seed))) return rc;
 
     c.have_table = false;
+    lz_limit_lift(c);
     memset(&c.geom, 0, sizeof(c.geom));
     c.geom.tlen = tlen; c.geom.start = start; c.geom.end = end; c.geom.step = step; c.geom.seed = *seed;
     memcpy(c.geom.char_to_bits, char_to_bits, 256);
@@ -348,6 +349,7 @@ extern "C" int lzgpu_target_upload(const uint8_t* t, uint32_t tlen)
     if (!t) return lz_fail(LZGPU_ERR_ARG, "null argument");
     if (tlen >= 0x7FFFFFFFu) return LZGPU_NH_SIZE;
     c.have_table = false;
+    lz_limit_lift(c);
     memset(&c.geom, 0, sizeof(c.geom));
     c.geom.tlen = tlen;
     return slot_upload(c, c.target, t, tlen, true);
@@ -379,6 +381,7 @@ extern "C" int lzgpu_table_rebuild(void)
     LzCtx& c = g_ctx;
     if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "no position table");
     int rc = lz_bind_thread(); if (rc) return rc;
+    lz_limit_lift(c);
     rc = lzk_table_build(c);
     if (!rc) c.geom.num_words = c.num_words;
     return rc;
@@ -418,6 +421,7 @@ extern "C" int lzgpu_table_adopt(const lz_table_geom* g)
     int rc = require_init(); if (rc) return rc;
     LzCtx& c = g_ctx;
     if (!g) return LZGPU_ERR_ARG;
+    lz_limit_lift(c);                                           // (before the seed changes: the buffers go back where they belong)
     if ((rc = lzh_seed_to_dev(&g->seed, c.seed))) return rc;
     c.have_table = false; c.geom = *g; c.num_words = g->num_words; c.table_gen++;
     size_t total = (size_t)g->tlen + 2 * LZ_SEQ_PAD + 16;
@@ -437,8 +441,8 @@ extern "C" int lzgpu_table_buffers(void* dev_ptr[3], uint64_t bytes[3])
     LzCtx& c = g_ctx;
     if (!c.target.have_raw || !c.wstart.p) return lz_fail(LZGPU_ERR_STATE, "no table buffers");
     dev_ptr[0] = c.target.raw_base(); bytes[0] = c.geom.tlen;
-    dev_ptr[1] = c.wstart.p;          bytes[1] = ((uint64_t)(1u << c.seed.weight) + 1) * 4;
-    dev_ptr[2] = c.wpos.p;            bytes[2] = (uint64_t)c.num_words * 4;
+    dev_ptr[1] = c.built_wstart().p;  bytes[1] = ((uint64_t)(1u << c.seed.weight) + 1) * 4;      // (the table as it was built, also under a limit)
+    dev_ptr[2] = c.built_wpos().p;    bytes[2] = (uint64_t)c.built_num_words() * 4;
     return 0;
 }
 
@@ -447,6 +451,7 @@ extern "C" int lzgpu_table_commit(void)
     LzCtx& c = g_ctx;
     if (!c.target.have_raw || !c.wstart.p) return lz_fail(LZGPU_ERR_STATE, "no table buffers");
     { int rc = lz_bind_thread(); if (rc) return rc; }
+    lz_limit_lift(c);
     // the entropy finish needs the target bytes on the host as well (the target itself does not
     // change between commits of the same geometry: copied back once)
     if (c.target.host.size() != c.geom.tlen) {
@@ -456,6 +461,61 @@ extern "C" int lzgpu_table_commit(void)
     }
     c.table_gen++;                                              // (the caller wrote wpos)
     c.have_table = true;
+    return 0;
+}
+
+// ---- the word-count limit (lastz --maxwordcount)
+// limit_position_table(pt, limit, 0) (src/pos_table.c:1763-1948; called at src/lastz.c:1219-1221): the searches read a copy of
+// the table without the lists of more than `limit` entries; the table as it was built stays where export / geom / buffers /
+// save / share find it, and every call that makes a table ends the limit.
+extern "C" int lzgpu_table_limit(uint32_t limit)
+{
+    LzCtx& c = g_ctx;
+    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "no position table");
+    int rc = lz_bind_thread(); if (rc) return rc;
+    if (limit == c.limit) return 0;
+    lz_limit_lift(c);
+    return limit ? lzk_table_limit(c, limit) : 0;
+}
+
+// position_table_count_distribution (src/pos_table.c:2064-2140) of the table as it was built.  Both out arrays are released
+// with lzgpu_free().
+extern "C" int lzgpu_table_count_distribution(uint32_t** count, uint32_t** words, uint32_t* n)
+{
+    LzCtx& c = g_ctx;
+    if (!count || !words || !n) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    *count = *words = nullptr; *n = 0;
+    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "no position table");
+    int rc = lz_bind_thread(); if (rc) return rc;
+    std::vector<u32> cn, wd;
+    if ((rc = lzk_table_count_distribution(c, cn, wd))) return rc;
+    const size_t bytes = (cn.size() ? cn.size() : 1) * sizeof(u32);
+    u32* a = (u32*)malloc(bytes); u32* b = (u32*)malloc(bytes);
+    if (!a || !b) { free(a); free(b); return lz_fail(LZGPU_ERR_OOM, "host malloc failed"); }
+    if (!cn.empty()) { memcpy(a, cn.data(), cn.size() * sizeof(u32)); memcpy(b, wd.data(), wd.size() * sizeof(u32)); }
+    *count = a; *words = b; *n = (uint32_t)cn.size();
+    return 0;
+}
+
+// find_position_table_limit(pt, keep) (src/pos_table.c:2000-2034; called at src/lastz.c:1215-1218) on the table as it was
+// built, in the reference's own arithmetic: unspos (u32) products and sums, the float product numPositions * keep, ceil in double
+extern "C" int lzgpu_table_find_limit(float keep, uint32_t* limit)
+{
+    LzCtx& c = g_ctx;
+    if (!limit) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    *limit = 0;
+    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "no position table");
+    int rc = lz_bind_thread(); if (rc) return rc;
+    std::vector<u32> cn, wd;
+    if ((rc = lzk_table_count_distribution(c, cn, wd))) return rc;
+    u32 num_positions = 0;
+    for (size_t k = 0; k < cn.size(); k++) num_positions += cn[k] * wd[k];
+    const float prod = (float)num_positions * keep;             // (numPositions * keep: unspos times float is a float product)
+    u32 min_to_keep = (u32)ceil((double)prod);
+    for (size_t k = 0; k < cn.size(); k++) {
+        if (cn[k] * wd[k] >= min_to_keep) { *limit = cn[k]; break; }
+        min_to_keep -= cn[k] * wd[k];
+    }
     return 0;
 }
 

@@ -109,7 +109,7 @@ int lzk_table_export(LzCtx& c, u32* last_dev, u32* prev_dev, u32 prev_entries)
     if (prev_dev) LZ_HIP(hipMemsetAsync(prev_dev, 0, (size_t)prev_entries * 4, c.stream));
     u32 adj = c.geom.start - (c.geom.start % c.geom.step);
     hipLaunchKernelGGL(k_table_export, dim3((nwords + LZ_TPB - 1) / LZ_TPB), dim3(LZ_TPB), 0, c.stream,
-                       c.wstart.as<u32>(), c.wpos.as<u32>(), nwords, adj, c.geom.step, last_dev, prev_dev);
+                       c.built_wstart().as<u32>(), c.built_wpos().as<u32>(), nwords, adj, c.geom.step, last_dev, prev_dev);   // (not a limited copy)
     LZ_HIP(hipGetLastError());
     return 0;
 }

@@ -75,7 +75,7 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 # every symbol include/lzgpu.h declares (tests check that the library exports all of them)
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
            "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_table_num_words",
-           "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_device_copy",
+           "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_table_limit", "lzgpu_table_find_limit", "lzgpu_table_count_distribution", "lzgpu_device_copy",
            "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
@@ -192,6 +192,30 @@ class Lib:
 
     def table_num_words(self):
         return int(self.L.lzgpu_table_num_words())
+
+    def table_limit(self, limit):
+        """lastz --maxwordcount=<limit>: from now on the searches see the table without the words that occur more than
+        `limit` times (0 lifts the limit); the unlimited table stays resident and is what export / geom / buffers / save describe"""
+        self.L.lzgpu_table_limit.argtypes = [C.c_uint32]
+        self._check(self.L.lzgpu_table_limit(limit), "lzgpu_table_limit")
+
+    def table_find_limit(self, keep):
+        """lastz --maxwordcount=<p>%: the limit find_position_table_limit gives for keep = p / 100 on the unlimited table"""
+        self.L.lzgpu_table_find_limit.argtypes = [C.c_float, C.POINTER(C.c_uint32)]
+        out = C.c_uint32()
+        self._check(self.L.lzgpu_table_find_limit(C.c_float(keep), C.byref(out)), "lzgpu_table_find_limit")
+        return int(out.value)
+
+    def table_count_distribution(self):
+        """-> (the distinct list lengths > 0 of the unlimited table in increasing order, the number of words that have each)"""
+        self.L.lzgpu_table_count_distribution.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
+        a = C.c_void_p(); b = C.c_void_p(); n = C.c_uint32()
+        self._check(self.L.lzgpu_table_count_distribution(C.byref(a), C.byref(b), C.byref(n)), "lzgpu_table_count_distribution")
+        count = np.zeros(n.value, dtype=np.uint32); words = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            C.memmove(_ptr(count), a, 4 * n.value); C.memmove(_ptr(words), b, 4 * n.value)
+        self.L.lzgpu_free(a); self.L.lzgpu_free(b)
+        return count, words
 
     def table_export(self, prev_entries):
         last = np.zeros(1 << self._weight, dtype=np.uint32)
