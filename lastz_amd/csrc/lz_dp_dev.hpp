@@ -440,7 +440,12 @@ LZ_HD void lz_dp_run(X& x, SH& sh, const LzDpParams& P, const LzDpJob& J,
                 first = x.uni(first); last = x.uni(last); cmax = x.uni(cmax); ccol = x.uni(ccol);
                 q1 = LZ_PHASE_CLOCK();
                 const u32 iter = RYi - LY0;
-                ct.cells += iter;
+                // "DP cells visited" (:3776) counts the columns the reference's loop reaches, and that loop also stops behind column N
+                // (:3683, "b - B <= N + 1").  RY passes N + 1 when a right bound lies beyond the job's last column -- an alignment in the
+                // next partition of the query: NN = R - 1 > N below -- so the row swept here is wider than the reference's by cells that
+                // cannot win (their B class is the separator's) and must not be counted.
+                const u32 col_end = RYi < N + 1 ? RYi : N + 1;
+                ct.cells += col_end > LY0 ? col_end - LY0 : 0u;
                 u32 tb_used = ct.tb_used + iter;
                 s32 best = best0;
                 if (cmax >= best0) { best = cmax; ct.best = cmax; ct.end1 = row; ct.end2 = ccol; }      // :3731-3735

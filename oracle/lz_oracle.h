@@ -155,6 +155,23 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
                            uint32_t tb_size,
                            lzo_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops,
                            lzo_gapped_stats* stats);
+/* The same on sequences that may be partitioned ("file[multi]"), with the trivial alignments of identical sequences
+ * and partitions (src/gapped_extend.c:1123-1281, 1354-1372, 1475-1545); the two above are calls of it.
+ * sep1 / sep2: the sepBefore of every partition plus the final NUL, n = 0 without partitions.  strands_differ:
+ * seq1->revCompFlags != seq2->revCompFlags.  inhibit_trivial: trivial alignments are dropped from the output (they
+ * still bound the others).  The reference's delayed check under inhibit_trivial compares sequence names, which are
+ * not passed here: an alignment that meets every other condition of it (one diagonal piece over a whole partition
+ * pair of equal length and equal bytes) stays in the output and sets *trivial_candidate (may be NULL).
+ * Returns 0, or 2 when an anchor lies in no partition. */
+int lzo_gapped_extend_parts(const uint8_t* t, uint32_t tlen, const uint8_t* q, uint32_t qlen,
+                            const int32_t* sub, int32_t gap_open, int32_t gap_extend,
+                            lzo_segment* anchors, uint32_t n_anchors,
+                            int32_t ydrop, int trim_to_peak, int all_bounds, int32_t score_thresh,
+                            uint32_t tb_size,
+                            const uint32_t* sep1, uint32_t n_sep1, const uint32_t* sep2, uint32_t n_sep2,
+                            int strands_differ, int inhibit_trivial,
+                            lzo_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops,
+                            lzo_gapped_stats* stats, int* trivial_candidate);
 
 #ifdef __cplusplus
 }

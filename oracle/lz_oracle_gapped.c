@@ -2,7 +2,11 @@
  *
  * Restates the gapped stage of the reference (lastz 1.04.58, src/gapped_extend.c):
  *   - reduce_to_points / segment_peak            :463-559
- *   - gapped_extend (anchor loop, non-partitioned, non-identical sequences) :1012-1604
+ *   - gapped_extend (anchor loop; the limits of partitioned sequences; the trivial alignments of identical
+ *     sequences and partitions; what inhibitTrivial drops)       :1012-1604
+ *   - identical_sequences, identical_partitioned_sequences, identical_partition_of_sequence,
+ *     score_identical_partition(_of)              :1886-2249
+ *   - lookup_partition                            src/sequences.c:6536-6612
  *   - batched_segments sort order                :1633-1675, src/segment.c:1748-1771
  *   - ydrop_align, lop_initial/final_indels      :2459-2683
  *   - ydrop_one_sided_align                      :3388-3868  (macro "prune" :2977-2987)
@@ -100,7 +104,7 @@ typedef struct galn {
     uint32_t pos1, pos2, end1, end2;
     aseg *first, *last;
     escript* script; int32_t s; uint32_t beg1, beg2, aend1, aend2;   /* the alignel */
-    int have_align;
+    int have_align, trivial, dropped;
     struct galn *left_align1, *right_align1, *left_align2, *right_align2;
     aseg *left_seg1, *right_seg1, *left_seg2, *right_seg2;
     struct galn *next, *prev;
@@ -682,11 +686,96 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
                            lzo_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops,
                            lzo_gapped_stats* stats)
 {
+    return lzo_gapped_extend_parts(t, tlen, q, qlen, sub, gap_open, gap_extend, anchors, n_anchors, ydrop, trim_to_peak,
+                                   all_bounds, score_thresh, tb_size, NULL, 0, NULL, 0, /* strands_differ */ 0,
+                                   /* inhibit_trivial */ 0, out, n_out, ops, n_ops, stats, NULL);
+}
+
+/* ------------------------------------------- partitions, trivial alignments */
+
+static uint8_t fold_upper(uint8_t c) { return (c >= 'a' && c <= 'z') ? (uint8_t)(c - 'a' + 'A') : c; }   /* dna_toupper */
+
+/* lookup_partition (src/sequences.c:6536-6612) as a linear walk: the partition that holds pos strictly between its
+ * separators, -1 for a position on a separator or outside every partition (the reference dies there) */
+static int part_holding(const uint32_t* sep, uint32_t n_sep, uint32_t pos)
+{
+    for (uint32_t ix = 0; ix + 1 < n_sep; ix++)
+        if (sep[ix] < pos && pos < sep[ix + 1]) return (int)ix;
+    return -1;
+}
+
+/* the comparison loop of identical_sequences / identical_partitioned_sequences / identical_partition_of_sequence
+ * (:1915-1920, :1986-1991, :2114-2119) */
+static int same_folded(const uint8_t* a, const uint8_t* b, uint32_t len)
+{
+    for (uint32_t ix = 0; ix < len; ix++) if (fold_upper(a[ix]) != fold_upper(b[ix])) return 0;
+    return 1;
+}
+
+/* the scoring loop of identical_sequences / score_identical_partition(_of) (:1922-1928, :2177-2183, :2239-2245):
+ * positive scores saturate at bestPossibleScore */
+static int32_t identity_score(const int32_t* sub, const uint8_t* a, const uint8_t* b, uint32_t len)
+{
+    const int32_t best_possible = 0x7FFFFFFF;
+    int32_t s = 0;
+    for (uint32_t ix = 0; ix < len; ix++) {
+        int32_t w = SUB(sub, fold_upper(a[ix]), fold_upper(b[ix]));
+        if (s == best_possible) ;
+        else if (w <= 0 || s < best_possible - w) s += w;
+        else s = best_possible;
+    }
+    return s;
+}
+
+/* one trivial alignment into slot mp and into the ordered lists, src/gapped_extend.c:1159-1186 / 1200-1230 / 1247-1277:
+ * one diagonal segment, a script of `len` substitutions, a score raised to the threshold "so it won't be discarded" */
+static void add_trivial(galn* mp, galn** p_obi, galn** p_oed, uint32_t pos1, uint32_t pos2, uint32_t len,
+                        int32_t s, int32_t score_thresh)
+{
+    mp->pos1 = pos1; mp->pos2 = pos2; mp->end1 = pos1 + len - 1; mp->end2 = pos2 + len - 1;
+    mp->left_align1 = mp->left_align2 = mp->right_align1 = mp->right_align2 = NULL;
+    mp->left_seg1 = mp->left_seg2 = mp->right_seg1 = mp->right_seg2 = NULL;
+    mp->first = NULL;
+    save_seg(mp, mp->pos1, mp->pos2, mp->end1, mp->end2);
+    insert_align(mp, p_obi, p_oed);
+    mp->last = mp->first;
+    mp->first->prev = mp->last->next = NULL;
+    mp->script = es_new();
+    es_add(mp->script, OP_SUB, len);                                          /* edit_script_sub */
+    mp->beg1 = pos1 + 1; mp->beg2 = pos2 + 1; mp->aend1 = pos1 + len; mp->aend2 = pos2 + len;
+    mp->s = (s < score_thresh) ? score_thresh : s;
+    mp->have_align = 1;
+    mp->trivial = 1;
+}
+
+/* The gapped stage on sequences that may be partitioned ("file[multi]": NUL, record, NUL, record, ..., NUL).
+ * sep1 / sep2: the sepBefore of every partition plus the final NUL (partition k lies strictly between sep[k] and
+ * sep[k + 1]); n_sep == 0 for a sequence without partitions.  strands_differ: seq1->revCompFlags != seq2->revCompFlags.
+ * inhibit_trivial: gapped_extend's inhibitTrivial.  Restated from src/gapped_extend.c:
+ *   - the limits of every extension are those of the partitions holding the anchor              :1354-1372
+ *   - trivial alignments go in front of the anchor loop: identical unpartitioned sequences, seq2 equal to a
+ *     partition of seq1 (the first such one), every partition pair (k, k) identical              :1123-1281
+ *   - at output trivial alignments are dropped under inhibit_trivial                             :1483-1484
+ *   - the delayed check (:1485-1545) compares sequence NAMES, which this interface does not have: alignments that
+ *     pass every other test of it (one diagonal segment over a whole partition pair of equal length with equal
+ *     bytes) are KEPT in the output and *trivial_candidate is set, so the caller can tell that the reference's
+ *     answer depends on the names.
+ * Returns 0, or 2 for an anchor that lies in no partition (the reference dies in lookup_partition). */
+int lzo_gapped_extend_parts(const uint8_t* t, uint32_t tlen, const uint8_t* q, uint32_t qlen,
+                            const int32_t* sub, int32_t gap_open, int32_t gap_extend,
+                            lzo_segment* anchors, uint32_t n_anchors,
+                            int32_t ydrop, int trim_to_peak, int all_bounds, int32_t score_thresh, uint32_t tb_size,
+                            const uint32_t* sep1, uint32_t n_sep1, const uint32_t* sep2, uint32_t n_sep2,
+                            int strands_differ, int inhibit_trivial,
+                            lzo_align** out, uint64_t* n_out, uint32_t** ops, uint64_t* n_ops,
+                            lzo_gapped_stats* stats, int* trivial_candidate)
+{
     lzo_gapped_stats st; memset(&st, 0, sizeof(st));
     *out = NULL; *n_out = 0; *ops = NULL; *n_ops = 0;
-    if (tlen == qlen && memcmp(t, q, tlen) == 0) return 1;   /* identical sequences: trivial
-                                                                self-alignment path not restated */
+    if (trivial_candidate) *trivial_candidate = 0;
     if (tb_size == 0) tb_size = 80u * 1024u * 1024u;          /* src/lastz.c:395 */
+    const int parted1 = n_sep1 >= 2, parted2 = n_sep2 >= 2;   /* sp1->p != NULL, sp2->p != NULL */
+    const uint32_t np1 = parted1 ? n_sep1 - 1 : 0, np2 = parted2 ? n_sep2 - 1 : 0;
 
     uint8_t* rev1 = (uint8_t*)malloc((size_t)tlen + 1);       /* copy_reverse_of_string */
     uint8_t* rev2 = (uint8_t*)malloc((size_t)qlen + 1);
@@ -695,7 +784,10 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
     rev1[tlen] = 0; rev2[qlen] = 0;
 
     qsort(anchors, n_anchors, sizeof(lzo_segment), by_decreasing_score);       /* :1675 */
-    galn* msp = (galn*)calloc((size_t)n_anchors + 1, sizeof(galn));
+    uint32_t extra = 1;                                                        /* :1069-1076 */
+    if (parted1 && parted2) extra = (np2 < np1) ? np2 : np1;
+    const uint32_t n_slots = n_anchors + extra;
+    galn* msp = (galn*)calloc((size_t)n_slots + 1, sizeof(galn));
     for (uint32_t k = 0; k < n_anchors; k++) { msp[k].pos1 = anchors[k].pos1; msp[k].pos2 = anchors[k].pos2; }
     st.anchors = n_anchors;
 
@@ -706,7 +798,40 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
     io.trim_to_peak = trim_to_peak;
     io.tb = (uint8_t*)malloc(tb_size); io.tb_size = tb_size; io.st = &st;
 
+    /* which trivial alignments there are, :1123-1147 */
+    int partitioned_triviality = 0, trivial_part = -1;
+    int delayed_check = inhibit_trivial && (parted1 || parted2);
+    if (parted1 && !parted2) {
+        if (!strands_differ)                                                   /* identical_partition_of_sequence */
+            for (uint32_t k = 0; k < np1 && trivial_part < 0; k++) {
+                uint32_t len1 = sep1[k + 1] - (sep1[k] + 1);
+                if (len1 == qlen && same_folded(t + sep1[k] + 1, q, len1)) trivial_part = (int)k;
+            }
+        partitioned_triviality = trivial_part != -1;
+        delayed_check = inhibit_trivial && !partitioned_triviality;
+    } else if (parted1 && parted2) {
+        partitioned_triviality = !strands_differ && np1 == np2;                /* identical_partitioned_sequences */
+        for (uint32_t k = 0; partitioned_triviality && k < np1; k++) {
+            uint32_t len1 = sep1[k + 1] - (sep1[k] + 1), len2 = sep2[k + 1] - (sep2[k] + 1);
+            if (len1 != len2 || !same_folded(t + sep1[k] + 1, q + sep2[k] + 1, len1)) partitioned_triviality = 0;
+        }
+        delayed_check = inhibit_trivial && !partitioned_triviality;
+    }
+
     galn *obi = NULL, *oed = NULL;
+    uint32_t free_slot = n_anchors;
+    if (!parted1 && !parted2 && !strands_differ && tlen == qlen && same_folded(t, q, tlen))            /* :1152-1189 */
+        add_trivial(&msp[free_slot], &obi, &oed, 0, 0, tlen, identity_score(sub, t, q, tlen), score_thresh);
+    else if (partitioned_triviality && !parted2) {                                                      /* :1191-1233 */
+        uint32_t lo = sep1[trivial_part] + 1;
+        add_trivial(&msp[free_slot], &obi, &oed, lo, 0, qlen, identity_score(sub, t + lo, q, qlen), score_thresh);
+    } else if (partitioned_triviality && parted2)                                                       /* :1235-1281 */
+        for (uint32_t k = 0; k < np1; k++) {
+            uint32_t lo1 = sep1[k] + 1, lo2 = sep2[k] + 1, len = sep1[k + 1] - lo1;
+            add_trivial(&msp[free_slot++], &obi, &oed, lo1, lo2, len, identity_score(sub, t + lo1, q + lo2, len), score_thresh);
+        }
+
+    int rc = 0;
     for (uint32_t k = 0; k < n_anchors; k++) {
         galn* mp = &msp[k];
         if (!msp_left_right(obi, mp)) continue;
@@ -714,6 +839,16 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
         io.left_seg = mp->left_seg1; io.right_seg = mp->right_seg1;
         io.anchor1 = mp->pos1; io.anchor2 = mp->pos2;
         get_above_below(&io, obi, oed);
+        if (parted1) {                                                         /* :1354-1372 */
+            int p1 = part_holding(sep1, n_sep1, io.anchor1);
+            if (p1 < 0) { rc = 2; break; }
+            io.low1 = sep1[p1] + 1; io.high1 = sep1[p1 + 1];
+        }
+        if (parted2) {
+            int p2 = part_holding(sep2, n_sep2, io.anchor2);
+            if (p2 < 0) { rc = 2; break; }
+            io.low2 = sep2[p2] + 1; io.high2 = sep2[p2 + 1];
+        }
         ydrop_align(&io);
         format_alignment(&io, mp);
         mp->pos1 = io.start1; mp->pos2 = io.start2; mp->end1 = io.stop1; mp->end2 = io.stop2;
@@ -727,21 +862,33 @@ int lzo_gapped_extend_opts(const uint8_t* t, uint32_t tlen, const uint8_t* q, ui
         insert_align(mp, &obi, &oed);
     }
 
+    /* :1475-1566 */
     uint64_t na = 0, nops = 0;
-    for (galn* mp = obi; mp != NULL; mp = mp->next) if (mp->s >= score_thresh) { na++; nops += mp->script->len; }
+    for (galn* mp = obi; rc == 0 && mp != NULL; mp = mp->next) {
+        mp->dropped = 0;
+        if (mp->s < score_thresh || (inhibit_trivial && mp->trivial)) { mp->dropped = 1; continue; }
+        if (delayed_check && mp->last == mp->first && mp->first->type == DIAG_SEG) {              /* :1485-1545 */
+            uint32_t len1 = tlen, len2 = qlen;                                 /* trueLen of the sequence / partition */
+            if (parted1) { int p1 = part_holding(sep1, n_sep1, mp->pos1); len1 = (p1 < 0) ? 0xFFFFFFFFu : sep1[p1 + 1] - (sep1[p1] + 1); }
+            if (parted2) { int p2 = part_holding(sep2, n_sep2, mp->pos2); len2 = (p2 < 0) ? 0xFFFFFFFEu : sep2[p2 + 1] - (sep2[p2] + 1); }
+            if (len1 == len2 && mp->end1 + 1 - mp->pos1 == len1
+                && memcmp(t + mp->pos1, q + mp->pos2, len1) == 0 && trivial_candidate) *trivial_candidate = 1;
+        }
+        na++; nops += mp->script->len;
+    }
     lzo_align* res = (lzo_align*)malloc((na ? na : 1) * sizeof(lzo_align));
     uint32_t* op_buf = (uint32_t*)malloc((nops ? nops : 1) * sizeof(uint32_t));
     uint64_t ia = 0, io_ = 0;
-    for (galn* mp = obi; mp != NULL; mp = mp->next) {
-        if (mp->s < score_thresh) continue;
+    for (galn* mp = obi; rc == 0 && mp != NULL; mp = mp->next) {
+        if (mp->dropped) continue;
         res[ia].beg1 = mp->beg1; res[ia].beg2 = mp->beg2; res[ia].end1 = mp->aend1; res[ia].end2 = mp->aend2;
         res[ia].s = mp->s; res[ia].script_len = mp->script->len; res[ia].script_off = (uint32_t)io_;
         memcpy(op_buf + io_, mp->script->op, mp->script->len * sizeof(uint32_t));
         io_ += mp->script->len; ia++;
     }
-    for (uint32_t k = 0; k < n_anchors; k++) { if (msp[k].script) es_free(msp[k].script); free_segs(&msp[k]); }
+    for (uint32_t k = 0; k < n_slots; k++) { if (msp[k].script) es_free(msp[k].script); free_segs(&msp[k]); }
     free(msp); free(io.tb); free(rev1); free(rev2);
     *out = res; *n_out = na; *ops = op_buf; *n_ops = nops;
     if (stats) *stats = st;
-    return 0;
+    return rc;
 }

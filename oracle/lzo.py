@@ -93,6 +93,8 @@ def lib():
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                          C.POINTER(GappedStats)]
+    L.lzo_gapped_extend_parts.argtypes = L.lzo_gapped_extend_opts.argtypes[:14] + [
+        C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_int] + L.lzo_gapped_extend_opts.argtypes[14:] + [C.POINTER(C.c_int)]
     _LIB = L
     return L
 
@@ -211,16 +213,24 @@ def reduce_to_points(t, q, sub, segs):
 
 
 def gapped_extend(t, q, sub, anchors, gap_open=400, gap_extend=30, ydrop=9400, trim_to_peak=True,
-                  score_thresh=3000, tb_size=0, all_bounds=False):
-    """anchors: SEG_DTYPE array already reduced to points.  Returns (aligns, ops, stats)."""
+                  score_thresh=3000, tb_size=0, all_bounds=False, sep1=None, sep2=None, strands_differ=False,
+                  inhibit_trivial=False):
+    """anchors: SEG_DTYPE array already reduced to points.  sep1 / sep2: the separators of a [multi] sequence (sepBefore
+    of every partition plus the final NUL), None without partitions; strands_differ / inhibit_trivial as lz_gapped_args
+    has them.  Returns (aligns, ops, stats); stats["trivial_candidate"]: under inhibit_trivial the result holds an
+    alignment that the reference keeps or drops by the sequences' names (lzo_gapped_extend_parts)."""
     ta, qa = nul_terminated(t), nul_terminated(q)
     anchors = anchors.copy()
     out = C.c_void_p(); n = C.c_uint64(); ops = C.c_void_p(); nops = C.c_uint64()
-    st = GappedStats()
-    rc = lib().lzo_gapped_extend_opts(_ptr(ta), len(ta) - 1, _ptr(qa), len(qa) - 1, _ptr(sub),
-                                 gap_open, gap_extend, _ptr(anchors), len(anchors), ydrop,
-                                 int(trim_to_peak), int(all_bounds), score_thresh, tb_size,
-                                 C.byref(out), C.byref(n), C.byref(ops), C.byref(nops), C.byref(st))
+    st = GappedStats(); cand = C.c_int(0)
+    s1, s2 = (np.ascontiguousarray([] if x is None else x, dtype=np.uint32) for x in (sep1, sep2))
+    if (sep1 is not None and len(s1) < 2) or (sep2 is not None and len(s2) < 2):
+        raise ValueError("a partitioned sequence has at least two separators")
+    rc = lib().lzo_gapped_extend_parts(_ptr(ta), len(ta) - 1, _ptr(qa), len(qa) - 1, _ptr(sub),
+                                       gap_open, gap_extend, _ptr(anchors), len(anchors), ydrop,
+                                       int(trim_to_peak), int(all_bounds), score_thresh, tb_size,
+                                       _ptr(s1), len(s1), _ptr(s2), len(s2), int(strands_differ), int(inhibit_trivial),
+                                       C.byref(out), C.byref(n), C.byref(ops), C.byref(nops), C.byref(st), C.byref(cand))
     if rc != 0:
         raise RuntimeError(f"lzo_gapped_extend rc={rc}")
     al = np.zeros(n.value, dtype=ALIGN_DTYPE)
@@ -231,6 +241,7 @@ def gapped_extend(t, q, sub, anchors, gap_open=400, gap_extend=30, ydrop=9400, t
         C.memmove(_ptr(op), ops, nops.value * 4)
     lib().lzo_free(out); lib().lzo_free(ops)
     stats = {k: int(getattr(st, k)) for k, _ in GappedStats._fields_}
+    stats["trivial_candidate"] = int(cand.value)
     return al, op, stats
 
 

@@ -155,6 +155,13 @@ extern "C" void emul_gapped_stats(u64* out) { out[0] = g_stats.anchors; out[1] =
 
 static int g_all_bounds = 0, g_no_trim = 0;
 extern "C" void emul_gapped_options(int all_bounds, int no_trim) { g_all_bounds = all_bounds; g_no_trim = no_trim; }   // of the calls that follow
+// the separators of partitioned sequences and the two flags that go with them (lz_gapped_args), of the calls that follow; n == 0: no partitions
+static std::vector<u32> g_sep1, g_sep2; static int g_strands_differ = 0, g_inhibit_trivial = 0;
+extern "C" void emul_gapped_partitions(const u32* sep1, u32 n_sep1, const u32* sep2, u32 n_sep2, int strands_differ, int inhibit_trivial)
+{
+    g_sep1.assign(sep1, sep1 + (sep1 ? n_sep1 : 0)); g_sep2.assign(sep2, sep2 + (sep2 ? n_sep2 : 0));
+    g_strands_differ = strands_differ; g_inhibit_trivial = inhibit_trivial;
+}
 
 extern "C" int emul_gapped_extend(const u8* t, u32 tlen, const u8* q, u32 qlen, const s32* sub,
                                   s32 gap_open, s32 gap_extend, s32 ydrop, s32 score_thresh, u32 tb_len,
@@ -170,6 +177,9 @@ extern "C" int emul_gapped_extend(const u8* t, u32 tlen, const u8* q, u32 qlen, 
     ex.tb_len = tb_len ? tb_len : 80u * 1024 * 1024; ex.tb_slot = tb_slot ? tb_slot : (1u << 22);
     LzGappedParams G; G.t = t; G.tlen = tlen; G.q = q; G.qlen = qlen; G.sub = sub;
     G.gap_open = gap_open; G.gap_extend = gap_extend; G.ydrop = ydrop; G.score_thresh = score_thresh; G.window = window; G.all_bounds = g_all_bounds != 0;
+    if (!g_sep1.empty()) { G.sep1 = g_sep1.data(); G.n_sep1 = (u32)g_sep1.size(); }
+    if (!g_sep2.empty()) { G.sep2 = g_sep2.data(); G.n_sep2 = (u32)g_sep2.size(); }
+    G.strands_differ = g_strands_differ != 0; G.inhibit_trivial = g_inhibit_trivial != 0;
     if (reduce) lzh_reduce_to_points(t, q, sub, anchors, n_anchors);
     std::vector<lz_align> al; std::vector<u32> op;
     rc = lzh_gapped_extend(G, ex, anchors, n_anchors, al, op, g_stats);

@@ -138,6 +138,8 @@ def test_identical_sequences_get_the_trivial_alignment(gpu):
         al, ops = gpu.gapped_extend(sub, segs.copy(), q=q)
         assert len(al) == 1 and tuple(al[0][["beg1", "beg2", "end1", "end2"]]) == (1, 1, 50000, 50000)
         assert list(ops) == [(50000 << 2) | 3] and al[0]["s"] == int(sub[t & 0xDF, t & 0xDF].sum())
+        oal, oops, _ = lzo.gapped_extend(t, q, sub, lzo.reduce_to_points(t, q, sub, segs.view(lzo.SEG_DTYPE)))     # ... which is the oracle's answer too
+        assert len(oal) == 1 and (al == oal).all() and (ops == oops).all()
         al, ops = gpu.gapped_extend(sub, segs.copy(), q=q, inhibit_trivial=True)
         assert len(al) == 0
     al, _ = gpu.gapped_extend(sub, segs.copy(), q=t.copy(), strands_differ=True)     # not "identical" for the reference
