@@ -177,7 +177,6 @@ class Lib:
         self._keep["ctb"] = ctb
         self._check(self._f("table_prepare")(_ptr(t), len(t), start, end, _ptr(ctb), C.byref(sd), step),
                     "lzgpu_table_prepare")
-        self._weight = sd.weight_bits
 
     def target_patch(self, pos, values):
         """t[pos[k]] = values[k] in the resident target (a chore's fences); the table stays as it is"""
@@ -218,7 +217,13 @@ class Lib:
         return count, words
 
     def table_export(self, prev_entries):
-        last = np.zeros(1 << self._weight, dtype=np.uint32)
+        """last[] / prev[] of the resident table; last[] has one entry per word of the table's own seed -- whichever call
+        made the table: prepare, adopt or load"""
+        g = self.table_geom()
+        own = 1 + (g.end - (g.start - g.start % g.step)) // g.step   # what the library writes (src/pos_table.c:1065)
+        if prev_entries != own:
+            raise LzGpuError(f"table_export: the table has {own} prev entries, the caller expects {prev_entries}")
+        last = np.zeros(1 << g.seed.weight_bits, dtype=np.uint32)
         prev = np.zeros(prev_entries, dtype=np.uint32)
         self._check(self.L.lzgpu_table_export(_ptr(last), _ptr(prev)), "lzgpu_table_export")
         return last, prev
@@ -230,7 +235,6 @@ class Lib:
 
     def table_adopt(self, g):
         self._check(self.L.lzgpu_table_adopt(C.byref(g)), "lzgpu_table_adopt")
-        self._weight = g.seed.weight_bits
 
     def table_buffers(self):
         p = (C.c_void_p * 3)()
