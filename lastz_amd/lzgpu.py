@@ -460,6 +460,10 @@ class Lib:
     def set_hit_capacity(self, n):
         self._check(self._f("set_hit_capacity")(n), "set_hit_capacity")
 
+    def set_hsp_capacity(self, n):
+        """room for candidate HSPs (counted before entropy) of one search; a search that finds more is declined"""
+        self._check(self.L.lzgpu_set_hsp_capacity(n), "set_hsp_capacity")
+
     def set_dp_slot(self, nbytes):
         self._check(self.L.lzgpu_set_dp_slot(nbytes), "set_dp_slot")
 
