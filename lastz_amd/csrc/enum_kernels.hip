@@ -1,6 +1,7 @@
 // enum_kernels.hip -- gfx950 kernels of hit enumeration: the query's seed words sorted
 // inside blocks of positions, raw-hit counts per position and their scan, and the two fill kernels that materialise a
-// chunk's hits in discovery order.
+// chunk's hits in discovery order.  Steps 1 and 2 of k_fill_hits2's list enumeration are text it shares with k_scan_hits2
+// (scan_kernels.hip): the fragments lz_enum_lists.inc, lz_enum_place.inc and lz_enum_owners.inc, included inside the kernel.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -100,6 +101,9 @@ k_count_sorted_owned(const u32* __restrict__ sk, const u32* __restrict__ sv, u32
 // with two binary searches over its (descending) positions -- so, unlike k_count_sorted, the positions are read.  The 16
 // probes of a group go through their searches in lock step (lz_clip_runs): their bounds and then each step's 16 loads are
 // in flight together.  A position filter (LZ_SELF_WINDOW, lzgpu_seed_hit_search_within) is the same clip with constant bounds.
+// The group loop is the statement of lz_enum_lists.inc (every position takes part here, and the lists are always clipped); it
+// is written out and not included because with the fragment's text this kernel's machine code changes (as many instructions, another
+// body), and the fill kernels' fragments are held to the code they had.
 #define LZ_SELF_GROUP 16
 __global__ void __launch_bounds__(LZ_TPB)
 k_count_sorted_self(const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, u32 lo, LzSeedDev sd,
@@ -273,27 +277,12 @@ k_fill_hits(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
 }
 
 // ---- k_fill_hits2 (round 4): the same hits at the same places, the lists found through LDS instead of shuffles.
-// Round 2's fill (DESIGN_HISTORY.md) laid the 64 lists of four positions end to end and let every lane search the running totals for the list
-// holding its hit: 13 shuffles and two prefix sums per 64 hits, 150 VALU instructions per 64-hit trip for 16 bytes of
-// useful traffic per hit.  Here a wave takes its 64 sorted entries at once:
-//   1. every lane reads the CSR bounds of its position's probes (13 independent pairs of loads in flight per lane)
-//      and keeps the lengths; an exclusive wave scan of the lanes' totals places the positions' runs end to end
-//      (entry-major, probe order inside an entry = the reference's enumeration order inside a position);
-//   2. every list marks the cell of its first hit in own[] (its id); a prefix maximum over own[] -- ids grow along the
-//      concatenation -- leaves every cell with the id of the list that holds it: 16 marks and two passes over 128
-//      bytes per lane instead of a search per hit;
-//   3. lane t takes hits t, t + 64, ...: own[t] -> (list source - list start), (run's place in the key array - run
-//      start, pos2) from two small LDS tables -> one gather from wpos[], one key stored.  The
-//      stores of a wave are runs of consecutive keys (one run per position), as before.
-// A wave's LDS traffic is its own (no barrier: LDS operations of one wave execute in program order); concatenations
-// longer than LZ_F2_CAP hits (repeats) are taken in pieces; seeds with more than 16 probes in groups of 16.
-// k_scan_hits2 (the fused path, scan_kernels.hip) repeats steps 1 and 2 line for line with its own CAP -- as one pair of shared functions the
-// marks of step 2 compiled to predicated stores instead of branches and the kernel ran 1.5 % slower (profiles/seed_dedup_ab_series.json):
-// a change to either copy goes into both: k_fill_hits2 in enum_kernels.hip, k_scan_hits2 in scan_kernels.hip.
+// The scheme, steps 1 to 3, is told in lz_enum_place.inc.  Steps 1 and 2 are text that this kernel and k_scan_hits2 (the fused path,
+// scan_kernels.hip) include -- lz_enum_place.inc with lz_enum_lists.inc, and lz_enum_owners.inc; step 3 is the kernel's own: here one
+// gather from wpos[] and one key stored per hit.  The stores of a wave are runs of consecutive keys (one run per position), as before.
 #define LZ_F2_CAP   2560                             // k_fill_hits2's CAP: own[] 5 KiB + 4.5 KiB of tables per wave = four workgroups per CU (the 64 positions of a wave have 2.5 k hits on the 50 Mbp pair)
 #define LZ_F2_WORDS (LZ_F2_CAP / 2 / 64)             // 32-bit words of own[] per lane
-// SELF: a self-comparison (lz_common.hpp, LzSelfDev): step 1 clips every list to the hits that survive, before the
-// wave scan (k_count_sorted_self counted the same); the rest of the kernel is the same code.  Also the instantiation of a
+// SELF: a self-comparison (lz_common.hpp, LzSelfDev): step 1 clips every list to the hits that survive.  Also the instantiation of a
 // position filter (LZ_SELF_WINDOW): lz_self_bounds gives its constant window.
 template <bool SELF>
 __global__ void __launch_bounds__(LZ_TPB)
@@ -302,8 +291,9 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
              const u32* __restrict__ sk, const u32* __restrict__ sv, u32 n, const u64* __restrict__ off,
              u64 base, u64* __restrict__ keys, LzSelfDev self)
 {
-    __shared__ LzListWave<LZ_F2_CAP> shw[LZ_TPB / 64];
-    LzListWave<LZ_F2_CAP>& sh = shw[threadIdx.x >> 6];
+    constexpr int CAP = LZ_F2_CAP, WORDS = LZ_F2_WORDS;         // (the fragments' names, as in k_scan_hits2)
+    __shared__ LzListWave<CAP> shw[LZ_TPB / 64];
+    LzListWave<CAP>& sh = shw[threadIdx.x >> 6];
     unsigned short* const own = reinterpret_cast<unsigned short*>(sh.own32);
     const u32 lane = threadIdx.x & 63u;
     const u32 j = blockIdx.x * LZ_TPB + threadIdx.x;           // one sorted entry per lane (sk / sv: the chunk's range of the list)
@@ -316,73 +306,13 @@ k_fill_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
     if (SELF) lz_self_bounds(self, pos2, slo, shi);
     u32 carry = 0;                                              // hits of the lane's position in the probe groups already done
     for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {       // uniform trip count
-        // ---- 1. bounds of the lane's lists
-        // (every load of the group is issued before the first is used: a lane without a probe reads word 0's bounds and
-        // drops them)
-        u32 la[LZ_FILL_GROUP], len[LZ_FILL_GROUP]; u32 total = 0;
-#pragma unroll
-        for (int p = 0; p < LZ_FILL_GROUP; p++) {
-            const bool on = in && r + p < sd.nprobes;
-            const u32 w = on ? (w_l ^ sd.probe_xor[(r + p) & (LZ_MAX_PROBES - 1)]) : 0u;
-            la[p] = wstart[w]; len[p] = wstart[w + 1];
-        }
-#pragma unroll
-        for (int p = 0; p < LZ_FILL_GROUP; p++) {
-            const bool on = in && r + p < sd.nprobes;
-            len[p] = on ? len[p] - la[p] : 0u;
-            if (!SELF) total += len[p];
-        }
-        if (SELF) {
-            lz_clip_runs<LZ_FILL_GROUP>(wpos, la, len, slo, shi);
-#pragma unroll
-            for (int p = 0; p < LZ_FILL_GROUP; p++) total += len[p];
-        }
-        u32 inc = total;
-        LZ_WAVE_SCAN_U32(inc, total, lz_uadd)
-        const u32 E = inc - total;                              // start of the lane's run in the wave's concatenation
-        const u32 T = (u32)__builtin_amdgcn_readlane((int)inc, 63);
-        {
-            u32 S = E;
-#pragma unroll
-            for (int p = 0; p < LZ_FILL_GROUP; p++) { sh.lsrc[lane * LZ_FILL_GROUP + p] = la[p] - S; S += len[p]; }
-        }
-        sh.ent[lane] = make_uint2(dbase + carry - E, pos2);
-        // ---- 2. + 3., a piece of LZ_F2_CAP hits at a time
-        for (u32 cs = 0; cs < T; cs += LZ_F2_CAP) {              // uniform
-            const u32 tc = (T - cs < (u32)LZ_F2_CAP) ? T - cs : (u32)LZ_F2_CAP;
-            uint4* const mine = reinterpret_cast<uint4*>(sh.own32 + lane * LZ_F2_WORDS);
-#pragma unroll
-            for (int k = 0; k < LZ_F2_WORDS / 4; k++) mine[k] = make_uint4(0u, 0u, 0u, 0u);
-            __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            {
-                u32 S = E;
-#pragma unroll
-                for (int p = 0; p < LZ_FILL_GROUP; p++) {
-                    const u32 l = len[p];
-                    if (l && S < cs + tc && S + l > cs) own[(S > cs ? S : cs) - cs] = (unsigned short)(1u + lane * LZ_FILL_GROUP + (u32)p);
-                    S += l;
-                }
-            }
-            __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            // prefix maximum over own[]: the lane's 2 * LZ_F2_WORDS cells, then the lanes' last values, then the cells again
-            u32 wv[LZ_F2_WORDS];
-#pragma unroll
-            for (int k = 0; k < LZ_F2_WORDS / 4; k++) { const uint4 v = mine[k]; wv[4 * k] = v.x; wv[4 * k + 1] = v.y; wv[4 * k + 2] = v.z; wv[4 * k + 3] = v.w; }
-            u32 segmax = 0;
-#pragma unroll
-            for (int k = 0; k < LZ_F2_WORDS; k++) { const u32 m2 = lz_umax(wv[k] & 0xFFFFu, wv[k] >> 16); segmax = lz_umax(segmax, m2); }
-            u32 sinc = segmax;
-            LZ_WAVE_SCAN_U32(sinc, segmax, lz_umax)
-            u32 run = lz_dpp_u32<0x138, 0xf, 0xf>(0u, sinc);    // wave_shr:1: the maximum of the lanes below
-#pragma unroll
-            for (int k = 0; k < LZ_F2_WORDS; k++) {
-                const u32 a0 = lz_umax(wv[k] & 0xFFFFu, run), a1 = lz_umax(wv[k] >> 16, a0);
-                wv[k] = a0 | (a1 << 16); run = a1;
-            }
-#pragma unroll
-            for (int k = 0; k < LZ_F2_WORDS / 4; k++) mine[k] = make_uint4(wv[4 * k], wv[4 * k + 1], wv[4 * k + 2], wv[4 * k + 3]);
-            __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            // the hits of the piece, 64 per trip, consecutive lanes = consecutive hits; four trips' gathers in flight
+        // ---- 1. the lane's lists and their places in the wave's concatenation
+#include "lz_enum_place.inc"
+        // ---- 2. + 3., a piece of CAP hits at a time
+        for (u32 cs = 0; cs < T; cs += CAP) {                   // uniform
+            const u32 tc = (T - cs < (u32)CAP) ? T - cs : (u32)CAP;
+#include "lz_enum_owners.inc"
+            // ---- 3. the hits of the piece, 64 per trip, consecutive lanes = consecutive hits; four trips' gathers in flight
             // (a lane beyond the end of the piece reads the last hit again and stores nothing: no branch around the loads)
             for (u32 tb = 0; tb < tc; tb += 256u) {
                 u32 p1[4], p2[4], dst[4]; bool ok[4];

@@ -22,6 +22,7 @@ typedef int64_t  s64;
 
 #define LZ_MAX_PARTS   16
 #define LZ_MAX_PROBES  128
+#define LZ_FILL_GROUP  16                       // probes of a query position taken together: a lane each in k_fill_hits, a lane's 16 lists in k_fill_hits2 / k_scan_hits2 (lz_enum_lists.inc)
 #define LZ_DIAG_BITS   16                       // diagHashSize = 65536, src/diag_hash.h:56
 #define LZ_DIAG_SIZE   (1u << LZ_DIAG_BITS)
 #define LZ_NCLASS      32                       // score classes per axis (5 bits of the code byte)

@@ -27,8 +27,6 @@
 
 #define LZ_KEY_BIN(k)  ((u32)((k) >> 40) & 0xFFu)    // the partition of a hit: bits 8..15 of hashedDiag (k_scan_hits, k_partition)
 
-// 16 lanes per query position, one probe (exact word / transition flip) per lane: k_fill_hits, k_fill_hits2, k_scan_hits2
-#define LZ_FILL_GROUP 16
 // a wave's lists of k_fill_hits2 / k_scan_hits2 (enum_kernels.hip, scan_kernels.hip)
 template <int CAP> struct LzListWave {               // CAP: hits per piece of a wave's concatenation
     static_assert(CAP % 512 == 0, "whole 16-byte groups of own[] per lane");

@@ -1,6 +1,7 @@
 // scan_kernels.hip -- gfx950 kernels of phase A (DESIGN.md section 3, rows 4 and 5, and rows 2 + 4 and 5 of the fused form):
 // every hit's two gap-free scans, independent of the diagonal hash, in three scan modes; the scans that go on as tasks; and
-// the fused kernel that enumerates and scans in one launch.
+// the fused kernel that enumerates and scans in one launch (steps 1 and 2 of its list enumeration: the fragments lz_enum_place.inc with
+// lz_enum_lists.inc, and lz_enum_owners.inc, text shared with k_fill_hits2 of enum_kernels.hip).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <type_traits>
@@ -293,14 +294,12 @@ int lzk_scan_hits(LzCtx& c, int mode, const LzExtendParams& P, const LzLutParams
 // ------------------------------------------------------------------------------------------
 // The fused path of scan mode 0: hit enumeration and phase A in one kernel, over a context-inlined table.
 //   k_build_wctx          (table_kernels.hip) the 32 bytes of the target's 2-bit array around every table entry, beside the entry
-//   k_scan_hits2          k_fill_hits2's steps 1-2 (enum_kernels.hip: the same code), then per hit: wpos[e] + wctx[e] + the query windows
+//   k_scan_hits2          k_fill_hits2's steps 1-2 (lz_enum_place.inc, lz_enum_owners.inc: the same text), then per hit: wpos[e] + wctx[e] + the query windows
 //                         (which depend on pos2 alone: one line per entry), lz_scan_round<false>, ONE tagged 8-byte record at the
 //                         hit's place in discovery order.  No keys, no summaries, no partition bytes.  Persistent waves (the
 //                         64 KiB tables are loaded once per workgroup) that stride over the 64-entry groups of the sorted list.
 //   k_scan_tasks<0, true> replaces the provisional record a queued hit left.
 //   k_partition<true>     sorts the tagged records in place.
-// Steps 1 and 2 stay written twice -- shared functions ran 1.5 % slower (profiles/seed_dedup_ab_series.json) -- so a change to
-// either copy goes into both: k_fill_hits2 in enum_kernels.hip, k_scan_hits2 in scan_kernels.hip.
 // the loads of one trip of 64 hits (issued a trip ahead of the arithmetic)
 struct LzFuseTrip { u32 p1, pos2, dst; bool ok; LzWctx cx; LzVec16 ql, qr; };
 
@@ -335,69 +334,12 @@ k_scan_hits2(u32 lo, u32 i0, u32 i1, LzSeedDev sd,
         if (SELF) lz_self_bounds(self, pos2, slo, shi);
         u32 carry = 0;
         for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {
-            // ---- 1. bounds of the lane's lists (k_fill_hits2)
-            u32 la[LZ_FILL_GROUP], len[LZ_FILL_GROUP]; u32 total = 0;
-#pragma unroll
-            for (int p = 0; p < LZ_FILL_GROUP; p++) {
-                const bool on = in && r + p < sd.nprobes;
-                const u32 w = on ? (w_l ^ sd.probe_xor[(r + p) & (LZ_MAX_PROBES - 1)]) : 0u;
-                la[p] = wstart[w]; len[p] = wstart[w + 1];
-            }
-#pragma unroll
-            for (int p = 0; p < LZ_FILL_GROUP; p++) {
-                const bool on = in && r + p < sd.nprobes;
-                len[p] = on ? len[p] - la[p] : 0u;
-                if (!SELF) total += len[p];
-            }
-            if (SELF) {
-                lz_clip_runs<LZ_FILL_GROUP>(wpos, la, len, slo, shi);
-#pragma unroll
-                for (int p = 0; p < LZ_FILL_GROUP; p++) total += len[p];
-            }
-            u32 inc = total;
-            LZ_WAVE_SCAN_U32(inc, total, lz_uadd)
-            const u32 E = inc - total;
-            const u32 T = (u32)__builtin_amdgcn_readlane((int)inc, 63);
-            {
-                u32 S = E;
-#pragma unroll
-                for (int p = 0; p < LZ_FILL_GROUP; p++) { sh.lsrc[lane * LZ_FILL_GROUP + p] = la[p] - S; S += len[p]; }
-            }
-            sh.ent[lane] = make_uint2(dbase + carry - E, pos2);
+            // ---- 1. the lane's lists and their places in the wave's concatenation
+#include "lz_enum_place.inc"
             // ---- 2. + 3., a piece of CAP hits at a time
             for (u32 cs = 0; cs < T; cs += CAP) {                // uniform
                 const u32 tc = (T - cs < (u32)CAP) ? T - cs : (u32)CAP;
-                uint4* const mine = reinterpret_cast<uint4*>(sh.own32 + lane * WORDS);
-#pragma unroll
-                for (int k = 0; k < WORDS / 4; k++) mine[k] = make_uint4(0u, 0u, 0u, 0u);
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                {
-                    u32 S = E;
-#pragma unroll
-                    for (int p = 0; p < LZ_FILL_GROUP; p++) {
-                        const u32 l = len[p];
-                        if (l && S < cs + tc && S + l > cs) own[(S > cs ? S : cs) - cs] = (unsigned short)(1u + lane * LZ_FILL_GROUP + (u32)p);
-                        S += l;
-                    }
-                }
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                u32 wv[WORDS];
-#pragma unroll
-                for (int k = 0; k < WORDS / 4; k++) { const uint4 v = mine[k]; wv[4 * k] = v.x; wv[4 * k + 1] = v.y; wv[4 * k + 2] = v.z; wv[4 * k + 3] = v.w; }
-                u32 segmax = 0;
-#pragma unroll
-                for (int k = 0; k < WORDS; k++) { const u32 m2 = lz_umax(wv[k] & 0xFFFFu, wv[k] >> 16); segmax = lz_umax(segmax, m2); }
-                u32 sinc = segmax;
-                LZ_WAVE_SCAN_U32(sinc, segmax, lz_umax)
-                u32 run = lz_dpp_u32<0x138, 0xf, 0xf>(0u, sinc);
-#pragma unroll
-                for (int k = 0; k < WORDS; k++) {
-                    const u32 a0 = lz_umax(wv[k] & 0xFFFFu, run), a1 = lz_umax(wv[k] >> 16, a0);
-                    wv[k] = a0 | (a1 << 16); run = a1;
-                }
-#pragma unroll
-                for (int k = 0; k < WORDS / 4; k++) mine[k] = make_uint4(wv[4 * k], wv[4 * k + 1], wv[4 * k + 2], wv[4 * k + 3]);
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
+#include "lz_enum_owners.inc"
                 // ---- 3. the hits of the piece, 64 per trip: table entry + context + query windows -> both scans' first
                 // windows -> the tagged record.  Two register sets take turns: a trip's loads are issued before the
                 // arithmetic of the trip before it.  (A lane beyond the end of the piece loads the last hit again.)

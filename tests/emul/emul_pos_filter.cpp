@@ -7,7 +7,8 @@
 
 // The raw hits of a whole query against the table (wstart / wpos: CSR, descending positions inside a word) under the
 // target interval [t_start, t_end), or with filter == 0 every hit (lz_count_hits_at / lz_fill_hits_at):
-//   cnt[pos2]     = the LZ_HD count of the position;  cnt_grp[pos2] = the kernels' way (16 lists clipped together);
+//   cnt[pos2]     = the LZ_HD count of the position;  cnt_grp[pos2] = the kernels' way: the text k_fill_hits2 / k_scan_hits2
+//                   compile (lz_enum_lists.inc: 16 lists clipped together);
 //   keys          = the LZ_HD fill for pos2 = 0 .. qlen, one after the other (at most cap are written).
 // Returns the number of keys; *survives = what lz_window_self said (0: nothing was clipped, nothing can survive).
 extern "C" long long emul_pos_filter_hits(const u8* qcode, u32 qlen, u32 tlen, s32 length, s32 weight, s32 nparts, const s32* shift,
@@ -36,16 +37,11 @@ extern "C" long long emul_pos_filter_hits(const u8* qcode, u32 qlen, u32 tlen, s
         } else {
             cnt[pos2] = lz_count_hits_self_at(qcode, pos2, 0, sd, s, wstart, wpos, valid, packed);
             if (!valid) continue;
-            u32 blo, bhi, g = 0; lz_self_bounds(s, pos2, blo, bhi);
-            for (int r = 0; r < sd.nprobes; r += 16) {
-                u32 a[16], l[16];
-                for (int p = 0; p < 16; p++) {
-                    const bool on = r + p < sd.nprobes;
-                    const u32 w = on ? (packed ^ sd.probe_xor[r + p]) : 0u;
-                    a[p] = wstart[w]; l[p] = on ? wstart[w + 1] - a[p] : 0u;
-                }
-                lz_clip_runs<16>(wpos, a, l, blo, bhi);
-                for (int p = 0; p < 16; p++) g += l[p];
+            const bool in = true, SELF = true; const u32 w_l = packed;
+            u32 slo, shi, g = 0; lz_self_bounds(s, pos2, slo, shi);
+            for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {
+#include "../../lastz_amd/csrc/lz_enum_lists.inc"
+                g += total;
             }
             cnt_grp[pos2] = g;
             buf.assign(cnt[pos2], 0);

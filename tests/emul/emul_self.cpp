@@ -30,7 +30,8 @@ extern "C" void emul_clip_run(const u32* wpos, u32 a, u32 b, u32 lo, u32 hi, u32
 // A whole self search's raw hits on code bytes (bits 5-6 the base, bit 7 "not a seed byte"), for a contiguous seed of
 // length L (2L bits) with the exact word and the L single-transition probes:
 //   the table as k_table_words + the stable sort build it (descending positions inside a word);
-//   cnt[pos2]  = lz_count_hits_self_at,  cnt_grp[pos2] = the kernels' way (16 lists clipped together, lz_clip_runs<16>);
+//   cnt[pos2]  = lz_count_hits_self_at,  cnt_grp[pos2] = the kernels' way: the text k_fill_hits2 / k_scan_hits2 compile
+//                (lz_enum_lists.inc: 16 lists clipped together), one probe group after the other;
 //   keys       = lz_fill_hits_self_at for pos2 = L .. len, one after the other (at most cap);
 //   all_keys   = lz_fill_hits_at (no filter), likewise.
 // Returns the number of keys (clipped) and sets *n_all.
@@ -51,37 +52,33 @@ extern "C" long long emul_self_hits(const u8* tcode, const u8* qcode, u32 len, u
         if (p == 0) break;
     }
     std::stable_sort(kv.begin(), kv.end(), [](const std::pair<u32, u32>& a, const std::pair<u32, u32>& b) { return a.first < b.first; });
-    std::vector<u32> wstart(nwords + 1, 0), wpos(kv.size() + 1, 0);
-    for (size_t i = 0; i < kv.size(); i++) { wstart[kv[i].first + 1]++; wpos[i] = kv[i].second; }
-    for (u32 w = 0; w < nwords; w++) wstart[w + 1] += wstart[w];
+    std::vector<u32> wstart_v(nwords + 1, 0), wpos_v(kv.size() + 1, 0);
+    for (size_t i = 0; i < kv.size(); i++) { wstart_v[kv[i].first + 1]++; wpos_v[i] = kv[i].second; }
+    for (u32 w = 0; w < nwords; w++) wstart_v[w + 1] += wstart_v[w];
     const LzSelfDev s = make_self(mode, L, len, band, sep1, n1, sep2, n2);
+    const u32* const wstart = wstart_v.data(); const u32* const wpos = wpos_v.data();   // (the fragment's names)
     long long nk = 0, na = 0;
     std::vector<u64> buf;
     for (u32 pos2 = 0; pos2 <= len; pos2++) {
         bool valid; u32 packed;
-        cnt[pos2] = lz_count_hits_self_at(qcode, pos2, 0, sd, s, wstart.data(), wpos.data(), valid, packed);
+        cnt[pos2] = lz_count_hits_self_at(qcode, pos2, 0, sd, s, wstart, wpos, valid, packed);
         u32 g = 0;
         if (valid) {
-            u32 blo, bhi; lz_self_bounds(s, pos2, blo, bhi);
-            for (int r = 0; r < sd.nprobes; r += 16) {
-                u32 a[16], l[16];
-                for (int p = 0; p < 16; p++) {
-                    const bool on = r + p < sd.nprobes;
-                    const u32 w = on ? (packed ^ sd.probe_xor[r + p]) : 0u;
-                    a[p] = wstart[w]; l[p] = on ? wstart[w + 1] - a[p] : 0u;
-                }
-                lz_clip_runs<16>(wpos.data(), a, l, blo, bhi);
-                for (int p = 0; p < 16; p++) g += l[p];
+            const bool in = true, SELF = true; const u32 w_l = packed;
+            u32 slo, shi; lz_self_bounds(s, pos2, slo, shi);
+            for (int r = 0; r < sd.nprobes; r += LZ_FILL_GROUP) {
+#include "../../lastz_amd/csrc/lz_enum_lists.inc"
+                g += total;
             }
         }
         cnt_grp[pos2] = g;
         if (!valid) continue;
         buf.assign(cnt[pos2], 0);
-        lz_fill_hits_self_at(qcode, pos2, sd, s, wstart.data(), wpos.data(), buf.data());
+        lz_fill_hits_self_at(qcode, pos2, sd, s, wstart, wpos, buf.data());
         for (u64 k : buf) { if ((u64)nk < cap) keys[nk] = k; nk++; }
-        u32 full = lz_count_hits_at(qcode, pos2, 0, sd, wstart.data(), valid, packed);
+        u32 full = lz_count_hits_at(qcode, pos2, 0, sd, wstart, valid, packed);
         buf.assign(full, 0);
-        lz_fill_hits_at(qcode, pos2, sd, wstart.data(), wpos.data(), buf.data());
+        lz_fill_hits_at(qcode, pos2, sd, wstart, wpos, buf.data());
         for (u64 k : buf) { if ((u64)na < cap) all_keys[na] = k; na++; }
     }
     *n_all = na;
