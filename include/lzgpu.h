@@ -236,6 +236,25 @@ int lzgpu_seed_hit_search_self(const lz_search_args* args, const lz_self_args* s
 typedef struct lz_pos_filter { uint32_t t_start, t_end, q_start, q_end; } lz_pos_filter;
 int lzgpu_seed_hit_search_within(const lz_search_args* args, const lz_pos_filter* within, lz_hsp** out, uint64_t* n_out);
 
+/* ---- B2 with exact-match extension (lastz --exact=<length>) ---------------------------------------
+ * seed_hit_search for processor == process_for_simple_hit with gfExtend == gfexExact (src/seed_search.c:1056-1192): per raw
+ * hit in discovery order the diagEnd test (:1113), then match_extend_seed_hit (:3018-3254): the seed window is checked
+ * base by base, right to left (:3066-3078; a spaced or transition seed's hit need not be an exact match -- at the first
+ * mismatch, at query position m, the hit yields no HSP and diagEnd = max(diagEnd, m), :3230-3249); otherwise the hit is
+ * extended left while bases match, down to the old diagEnd and the start of either sequence (:3094-3129), and right to the
+ * end of either (:3146-3165), diagEnd = max(diagEnd, right end in the query) (:3175-3178), and it is an HSP iff
+ * length >= (unsigned) hsp_threshold (:3209), reported with the positions of its right end and score == length (:3197-3224).
+ * Two bases match iff match_bits[t] == match_bits[q] >= 0: match_bits is hp->charToBits (nuc_to_bits: lower case matches
+ * upper case; N, IUPAC codes and NUL match nothing, not even themselves), NOT the upperCharToBits the table was built with.
+ * A NUL matches nothing whatever match_bits says (:3122-3123, :3159-3160).
+ * Of args, hsp_threshold is the required length; sub, xdrop, entropic and extend are not read (sub may be NULL); query,
+ * query_slot, start and end are as in lzgpu_seed_hit_search.  HSPs come back in discovery order; lzgpu_last_hsp_order works
+ * afterwards.  Counters: words and raw_hits as in the plain search, hsps the number returned; extensions and bp_extended
+ * are NOT advanced by this entry point.
+ * Bucket owners (lzgpu_set_bucket_owner) return LZGPU_NH_UNSUPPORTED before any work; more candidates than the HSP capacity
+ * return LZGPU_NH_HSP_OVERFLOW.  Not combined with a self-comparison or a position filter. */
+int lzgpu_seed_hit_search_exact(const lz_search_args* args, const int8_t match_bits[256], lz_hsp** out, uint64_t* n_out);
+
 /* ---- B1 + B2 for many small rectangles of the two sequences at once ----------------------------
  * What src/tweener.c:769-829 (bounded_align) does for every in-between window of `lastz --inner=<score>`:
  * build_seed_position_table on target[t_off, t_off + t_len) with the inner seed, seed_hit_search of

@@ -592,7 +592,8 @@ u64 seed_hit_search
 		}
 
 	if ((pt != devTable) || (devTable == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
-	 || (processor != process_for_simple_hit) || (hp->gfExtend != gfexXDrop)
+	 || (processor != process_for_simple_hit) || ((hp->gfExtend != gfexXDrop) && (hp->gfExtend != gfexExact))
+	 || ((hp->gfExtend == gfexExact) && ((selfCompare) || (hp->posFilter) || (bandWidth != 0)))   /* --exact: alone, not with --self, --chores or --band */
 	 || (hp->hspThreshold.t != 'S') || ((hp->posFilter) && (selfCompare)) || (hp->minMatches >= 0) || (hp->reportEntropy)
 	 || ((!selfCompare) && (bandWidth != 0)) || (searchLimit != 0)
 	 || (seq2->fileType == seq_type_qdna) || (hp->seq1 != seq1) || (hp->seq2 != seq2)
@@ -609,7 +610,12 @@ u64 seed_hit_search
 	a.sub   = (const int32_t*) hp->scoring->sub;
 	a.xdrop = hp->xDrop;  a.hsp_threshold = hp->hspThreshold.s;  a.entropic = hp->entropicHsp;  a.extend = 1;
 
-	if (selfCompare)                                            /* --self (and --band): the hits seed_hit_below_diagonal drops, dropped on the device */
+	if (hp->gfExtend == gfexExact)                              /* --exact=<length>: match_extend_seed_hit (src/seed_search.c:3018-3254) on the device, under hp->charToBits */
+		{
+		rc = lzgpu_seed_hit_search_exact (&a, (const int8_t*) hp->charToBits, &h, &n);
+		if (rc < 0) suicidef ("lzgpu_seed_hit_search_exact: %s", lzgpu_last_error());
+		}
+	else if (selfCompare)                                       /* --self (and --band): the hits seed_hit_below_diagonal drops, dropped on the device */
 		{
 		lz_self_args sa;
 		uint32_t*    sep1, *sep2;
@@ -660,8 +666,8 @@ u64 seed_hit_search
 	empty_diag_hash ();                                        /* the reference's side effect, src/seed_search.c:362 */
 	for (k=0 ; k<n ; k++)                                      /* HSPs arrive in discovery order */
 		basesHit += (*hp->reporter) (hp->reporterInfo, h[k].pos1, h[k].pos2, h[k].length, h[k].score);
-	if ((n > 0) && (hp->anchors != NULL) && (*(hp->anchors) != NULL))
-		(*(hp->anchors))->haveScores = true;                   /* src/seed_search.c:2952-2953 */
+	if ((n > 0) && (hp->gfExtend == gfexXDrop) && (hp->anchors != NULL) && (*(hp->anchors) != NULL))
+		(*(hp->anchors))->haveScores = true;                   /* src/seed_search.c:2952-2953 (the X-drop routine's: match_extend_seed_hit sets nothing) */
 	lzgpu_free (h);
 	note ("search", "done on the GPU");
 	return basesHit;

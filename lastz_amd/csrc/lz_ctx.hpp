@@ -42,6 +42,8 @@ struct SeqSlot {                    // a sequence resident in HBM
     bool   have_nib = false;
     DevBuf two, spc;                // 2-bit codes and the 1-bit "not A,C,G,T" mask (lz_lut.hpp), rebuilt with the codes
     DevBuf two_x, spc_x;            // the same bytes in half-overlapping 64-byte blocks (k_overlap32; read by k_scan_hits for the target)
+    DevBuf mtwo, mspc;              // the match codes of an exact-match search (lz_exact.hpp): 2-bit codes and the 1-bit "matches nothing" mask, same layout as two / spc
+    uint64_t match_key = 0;         // hash of the match_bits they were made from; 0 = not made / the bytes changed since
     DevBuf occ_dev;                 // [256] u32: which byte values occur
     u8     occ[256] = { 0 };        // ... on the host
     bool   has_special = false;     // some byte of the sequence is outside the 2-bit alphabet
@@ -54,9 +56,9 @@ struct SeqSlot {                    // a sequence resident in HBM
     u8* code_base() const { return code.as<u8>() + LZ_SEQ_PAD; }
     void release()                  // every DevBuf above (a new one goes in here), and what says they hold something
     {
-        DevBuf* all[] = { &raw, &code, &dp, &nib, &two, &spc, &two_x, &spc_x, &occ_dev };
+        DevBuf* all[] = { &raw, &code, &dp, &nib, &two, &spc, &two_x, &spc_x, &mtwo, &mspc, &occ_dev };
         for (DevBuf* b : all) b->release();
-        have_raw = have_nib = false; code_key = dp_key = 0;
+        have_raw = have_nib = false; code_key = dp_key = match_key = 0;
     }
 };
 
@@ -118,6 +120,7 @@ struct LzCtx {
     std::vector<s32> lut_m4; s32 lut_xdrop = -1;   // likewise what lut was built from (empty: not built)
     DevBuf cls_t, cls_q, cls_tmp;   // the 256-byte class maps on the device: the target's, the query's, B3's (lz_encode_with, dp_stream)
     DevBuf win_tab;                 // the same for lzgpu_window_search (its own: the two callers may use different matrices)
+    DevBuf match_tmp;               // scratch of the match-code passes (lzgpu_seed_hit_search_exact): the class map, code bytes of one sequence, presence flags
     DevBuf hsp_out, hsp_count;      // candidates + counter
     DevBuf hsp_mc;                  // [n][5]: A/C/G/T match counts of the candidates (entropy inputs) + probe index
     DevBuf dev_counters;            // u64[8]
@@ -129,6 +132,7 @@ struct LzCtx {
     DevBuf win_jobs, win_scratch, win_out, win_count;
     bool win_attr_set = false;        // k_window_search's dynamic-LDS attribute has been set on this device context (lzgpu_shutdown clears it)
     bool settle_attr_set = false;     // likewise k_settle2's
+    bool settle_exact_attr_set = false;   // likewise k_settle_exact's
     u64 dp_longest[4] = { 0, 0, 0, 0 };   // lzgpu_dp_longest: rows, cells, sweep and traceback ticks of the DP that swept the most rows since the last reset
     // the two settings below keep their value across shutdown + init, as hit_capacity does
     u32 dp_slot_tb = 8u << 20;        // lzgpu_set_dp_slot: the uniform traceback slot (bytes) per DP
@@ -155,7 +159,7 @@ struct LzCtx {
     void release_device_memory()
     {
         DevBuf* all[] = { &wstart, &wpos, &full_wstart, &full_wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
-                          &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab,
+                          &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab, &match_tmp,
                           &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep,
                           &dp.jobs, &dp.ids, &dp.res, &dp.tab, &dp.tb, &dp.rows, &dp.ops, &dp.ops_off, &dp.ops_out, &dp.pieces, &dp.rings, &dp.sel_jobs, &dp.sel_res, &dp.problems,
                           &win_jobs, &win_scratch, &win_out, &win_count };
@@ -167,7 +171,7 @@ struct LzCtx {
         pinned = nullptr; pinned_words = 0;
         have_table = false; wctx_gen = 0; wctx_code_key = 0; limit = 0; full_num_words = 0;
         score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
-        win_attr_set = false; settle_attr_set = false;
+        win_attr_set = false; settle_attr_set = false; settle_exact_attr_set = false;
     }
 };
 
@@ -179,7 +183,7 @@ int lz_fail(int code, const char* fmt, ...);
 
 // ---- the seed stage's launchers: all asynchronous on c.stream (lzk_encode: or the stream it is given).  A launcher is passed what
 // varies per call -- the chunk, the kernels' parameters, the mode -- and reads the buffers that are members of LzCtx from c. ----
-struct LzChunk; struct LzLutParams;                  // lz_host.hpp, lz_lut.hpp
+struct LzChunk; struct LzLutParams; struct LzExactParams;     // lz_host.hpp, lz_lut.hpp, lz_exact.hpp
 #include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
 // seq_kernels.hip
 int lzk_encode(LzCtx& c, const u8* raw, u8* code, u32 len, const u8* cls256_dev, hipStream_t st = nullptr, KernelTimer* timer = nullptr);   // defaults: c.stream, c.timer
@@ -210,3 +214,6 @@ int lzk_partition(LzCtx& c, bool tagged, u64 n);     // c.keys + c.summ (or tagg
 int lzk_hist_scan(LzCtx& c, u64 n);                  // after the partition of the chunk: c.hist, c.hist_part, c.bin_base
 int lzk_settle(LzCtx& c, const LzExtendParams& P, u64 n, u32 out_cap);   // -> c.diag_end, c.hsp_out / c.hsp_count, c.dev_counters
 int lzk_hsp_match_counts(LzCtx& c, u32 n_rec, const SeqSlot& q);         // -> c.hsp_mc
+int lzk_settle_exact(LzCtx& c, const LzExactParams& P, u64 n, u32 out_cap);   // phase B of an exact-match search -> c.diag_end, c.hsp_out / c.hsp_count
+// exact_kernels.hip
+int lzk_scan_exact(LzCtx& c, const LzExactParams& P, u64 n);             // phase A of an exact-match search: c.keys -> c.summ (sized by the caller)

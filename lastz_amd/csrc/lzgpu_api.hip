@@ -16,6 +16,7 @@
 #include "lz_ctx.hpp"
 #include "lz_host.hpp"
 #include "lz_lut.hpp"
+#include "lz_exact.hpp"
 
 // ------------------------------------------------------------------------------ context
 
@@ -228,7 +229,7 @@ static int slot_upload(LzCtx& c, SeqSlot& s, const u8* bytes, u32 len, bool keep
     LZ_HIP(hipMemsetAsync(s.code.p, LZ_CODE_INVALID, total, st));
     if (len) LZ_HIP(hipMemcpyAsync(s.raw_base(), bytes, len, hipMemcpyHostToDevice, st));
     LZ_HIP(hipStreamSynchronize(st));
-    s.len = len; s.have_raw = true; s.code_key = 0; s.dp_key = 0;
+    s.len = len; s.have_raw = true; s.code_key = 0; s.dp_key = 0; s.match_key = 0;
     if (keep_host) s.host.assign(bytes, bytes + len); else s.host.clear();
     return 0;
 }
@@ -285,6 +286,33 @@ static int slot_encode(LzCtx& c, SeqSlot& s, const u8 cls[256], DevBuf& cls_dev)
     return 0;
 }
 
+// the match codes of slot s for an exact-match search (lz_exact.hpp), unless it holds those of the same match_bits already:
+// the encode and pack passes once more with the match classes, through scratch code bytes of the slot's geometry
+static int slot_match_encode(LzCtx& c, SeqSlot& s, const int8_t match_bits[256])
+{
+    u8 cls[256];
+    lz_exact_cls(match_bits, cls);
+    const uint64_t key = fnv1a(cls, 256);
+    if (s.match_key == key && s.mtwo.p && s.mspc.p) return 0;
+    int rc;
+    s.match_key = 0;
+    const size_t total = (size_t)s.len + 2 * LZ_SEQ_PAD + 16, code_at = 2048;     // scratch: class map | presence flags at 256 | code bytes at 2048
+    if ((rc = c.match_tmp.ensure(code_at + total))) return rc;
+    u8* const tmp = c.match_tmp.as<u8>();
+    u8* const code_base = tmp + code_at + LZ_SEQ_PAD;
+    LZ_HIP(hipMemcpyAsync(tmp, cls, 256, hipMemcpyHostToDevice, c.stream));
+    LZ_HIP(hipMemsetAsync(tmp + code_at, LZ_CODE_INVALID, total, c.stream));
+    LZ_HIP(hipStreamSynchronize(c.stream));          // cls is stack memory
+    if ((rc = lzk_encode(c, s.raw_base(), code_base, s.len, tmp))) return rc;
+    const u32 nmask = (u32)(((size_t)s.len + 2 * LZ_PAD2 + 7) / 8 + 16);          // (slot_encode's geometry of two / spc)
+    if ((rc = s.mtwo.ensure((size_t)nmask * 2 + 96))) return rc;
+    if ((rc = s.mspc.ensure((size_t)nmask + 96))) return rc;
+    LZ_HIP(hipMemsetAsync(s.mtwo.p, 0, (size_t)nmask * 2 + 96, c.stream));
+    LZ_HIP(hipMemsetAsync(s.mspc.p, 0xFF, (size_t)nmask + 96, c.stream));
+    if ((rc = lzk_pack2(c, code_base, s.raw_base(), s.len, s.mtwo.as<u8>(), s.mspc.as<u8>(), nmask, reinterpret_cast<u32*>(tmp + 256)))) return rc;
+    s.match_key = key;
+    return 0;
+}
 
 // (the two helpers of B3's set-up: on B3's stream, with B3's own class-table buffer and timer)
 int lz_slot_upload_public(LzCtx& c, SeqSlot& s, const u8* bytes, u32 len) { return slot_upload(c, s, bytes, len, false, c.dp_stream); }
@@ -371,7 +399,7 @@ extern "C" int lzgpu_target_patch(const uint32_t* pos, const uint8_t* bytes, uin
         LZ_HIP(hipMemcpyAsync(c.target.raw_base() + pos[k], &c.target.host[pos[k]], 1, hipMemcpyHostToDevice, c.stream));
     }
     LZ_HIP(hipStreamSynchronize(c.stream));
-    c.target.code_key = 0; c.target.dp_key = 0;
+    c.target.code_key = 0; c.target.dp_key = 0; c.target.match_key = 0;
     c.wctx_gen = 0; c.wctx_code_key = 0;
     return 0;
 }
@@ -429,7 +457,7 @@ extern "C" int lzgpu_table_adopt(const lz_table_geom* g)
     if ((rc = c.target.code.ensure(total))) return rc;
     LZ_HIP(hipMemsetAsync(c.target.raw.p, 0, total, c.stream));
     LZ_HIP(hipMemsetAsync(c.target.code.p, LZ_CODE_INVALID, total, c.stream));
-    c.target.len = g->tlen; c.target.have_raw = true; c.target.code_key = 0; c.target.dp_key = 0; c.target.host.clear();
+    c.target.len = g->tlen; c.target.have_raw = true; c.target.code_key = 0; c.target.dp_key = 0; c.target.match_key = 0; c.target.host.clear();
     if ((rc = c.wstart.ensure(((size_t)(1u << c.seed.weight) + 1) * 4))) return rc;
     if ((rc = c.wpos.ensure((size_t)(g->num_words ? g->num_words : 1) * 4))) return rc;
     LZ_HIP(hipStreamSynchronize(c.stream));
@@ -457,7 +485,7 @@ extern "C" int lzgpu_table_commit(void)
     if (c.target.host.size() != c.geom.tlen) {
         c.target.host.resize(c.geom.tlen);
         if (c.geom.tlen) LZ_HIP(hipMemcpy(c.target.host.data(), c.target.raw_base(), c.geom.tlen, hipMemcpyDeviceToHost));
-        c.target.code_key = 0; c.target.dp_key = 0;
+        c.target.code_key = 0; c.target.dp_key = 0; c.target.match_key = 0;
     }
     c.table_gen++;                                              // (the caller wrote wpos)
     c.have_table = true;
@@ -614,7 +642,10 @@ struct SeedSearch {                                             // a seed_search
     u64 total_hits = 0;
     std::vector<LzChunk> chunks; u64 max_chunk = 0;             // [i0,i1) in query positions with at most hit_capacity hits each
     int mode = 2; bool fused = false;                           // phase-A scan mode; k_scan_hits2 in the place of fill + scan
-    LzExtendParams P; LzLutParams Q;
+    const int8_t* match_bits = nullptr;                         // an exact-match search (lzgpu_seed_hit_search_exact): a->sub, xdrop, entropic and extend are not read
+    bool exact() const { return match_bits != nullptr; }
+    bool extend() const { return exact() || a->extend != 0; }
+    LzExtendParams P; LzLutParams Q; LzExactParams X;
     u32 out_cap = 0;
     std::vector<lz_hsp> plain;                                  // !a->extend: every hit
 };
@@ -641,6 +672,17 @@ static int ss_classes(LzCtx& c, SeedSearch& s)
 {
     const s32* sub = s.a->sub;
     int rc;
+    if (s.exact()) {
+        // the codes the enumeration reads (the table's char_to_bits, no score classes) and the match codes of both sequences
+        u8 cls[256];
+        lzh_make_cls(nullptr, c.geom.char_to_bits, cls);
+        if ((rc = slot_encode(c, c.target, cls, c.cls_t))) return rc;
+        if ((rc = slot_encode(c, *s.qs, cls, c.cls_q))) return rc;
+        if ((rc = slot_match_encode(c, c.target, s.match_bits))) return rc;
+        if ((rc = slot_match_encode(c, *s.qs, s.match_bits))) return rc;
+        g_hp.lap(0, "upload+classes+encode");
+        return 0;
+    }
     if (c.score_sub.size() != 65536 || memcmp(c.score_sub.data(), sub, 65536 * sizeof(s32)) != 0) {
         s32 tab[LZ_NCLASS * LZ_NCLASS];
         c.score_sub.clear();
@@ -729,6 +771,13 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
 {
     const lz_search_args* a = s.a;
     SeqSlot* qs = s.qs;
+    if (s.exact()) {                                            // k_scan_exact: no mode, no tables, never fused
+        LzExactParams& X = s.X;
+        X.t2 = c.target.mtwo.as<u8>(); X.tsp = c.target.mspc.as<u8>(); X.q2 = qs->mtwo.as<u8>(); X.qsp = qs->mspc.as<u8>();
+        X.tlen = c.geom.tlen; X.qlen = qs->len; X.seed_len = s.L; X.thr = (u32)a->hsp_threshold;      // src/seed_search.c:3209
+        s.fused = false;
+        return 0;
+    }
     LzExtendParams& P = s.P; LzLutParams& Q = s.Q;
     P.tcode = c.target.code_base(); P.tlen = c.geom.tlen;
     P.qcode = qs->code_base();      P.qlen = qs->len;
@@ -769,7 +818,7 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
 // ---- 6. the per-chunk buffers, sized once per search for the largest chunk
 static int ss_reserve(LzCtx& c, SeedSearch& s)
 {
-    const bool extend = s.a->extend != 0;
+    const bool extend = s.extend();
     const u64 max_chunk = s.max_chunk;
     int rc;
     if (max_chunk) {
@@ -785,6 +834,7 @@ static int ss_reserve(LzCtx& c, SeedSearch& s)
     }
     s.out_cap = (u32)std::min<u64>(c.hsp_capacity, 0xFFFFFFF0ull);
     if (extend && (rc = c.hsp_out.ensure((size_t)s.out_cap * sizeof(LzHspRec)))) return rc;
+    if (s.exact()) return max_chunk ? c.summ.ensure((size_t)max_chunk * 4) : 0;
     if (extend && max_chunk && (rc = s.fused ? lzk_fused_reserve(c, max_chunk) : lzk_scan_reserve(c, s.mode, max_chunk))) return rc;
     return 0;
 }
@@ -803,6 +853,16 @@ static int ss_chunk(LzCtx& c, SeedSearch& s, const LzChunk& ch)
     if ((rc = lzk_partition(c, s.fused, ch.nh))) return rc;
     if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
     return lzk_settle(c, s.P, ch.nh, s.out_cap);
+}
+// ... of an exact-match search: k_scan_exact and k_settle_exact in the places of the X-drop kernels, everything between them as it is
+static int ss_chunk_exact(LzCtx& c, SeedSearch& s, const LzChunk& ch)
+{
+    int rc;
+    if ((rc = lzk_fill_hits(c, s.lo, ch, s.n))) return rc;
+    if ((rc = lzk_scan_exact(c, s.X, ch.nh))) return rc;
+    if ((rc = lzk_partition(c, false, ch.nh))) return rc;
+    if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
+    return lzk_settle_exact(c, s.X, ch.nh, s.out_cap);
 }
 // ... of a search without extension (process_for_plain_hit): every hit is reported
 static int ss_chunk_plain(LzCtx& c, SeedSearch& s, const LzChunk& ch)
@@ -825,7 +885,12 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
     LZ_HIP(hipMemcpyAsync(&n_rec, c.hsp_count.p, 4, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
     g_hp.lap(4, "wait for GPU");
-    const bool gpu_counts = a->extend && n_rec > 0 && n_rec <= s.out_cap;
+    // (an exact-match search needs the discovery order only: of k_hsp_match_counts' output the probe index; score = length, no
+    // entropy, and the threshold was applied where the length was found)
+    const bool extend = s.extend();
+    const s32 K = s.exact() ? 0 : a->hsp_threshold;
+    const int entropic = s.exact() ? 0 : a->entropic;
+    const bool gpu_counts = extend && n_rec > 0 && n_rec <= s.out_cap;
     if (gpu_counts) {
         if ((rc = c.hsp_mc.ensure((size_t)n_rec * 20))) return rc;
         if ((rc = lzk_hsp_match_counts(c, n_rec, *s.qs))) return rc;
@@ -834,7 +899,7 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
     { std::lock_guard<std::mutex> lk(c.counters_m);
       c.counters.words += hc[2]; c.counters.raw_hits += s.total_hits;
       c.counters.extensions += hc[0]; c.counters.bp_extended += hc[1]; }
-    if (!a->extend) return lz_hsps_out(s.plain, out, n_out);
+    if (!extend) return lz_hsps_out(s.plain, out, n_out);
     if (n_rec > s.out_cap) return LZGPU_NH_HSP_OVERFLOW;
 
     std::vector<LzHspRec> recs(n_rec);
@@ -846,7 +911,7 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
     g_hp.lap(5, "copy candidates");
     std::vector<lz_hsp> fin;
     if ((rc = lzh_finish_hsps(recs.data(), n_rec, c.target.host.data(), s.qhost, c.seed, c.geom.char_to_bits,
-                              a->hsp_threshold, a->entropic, fin, gpu_counts ? mc.data() : nullptr, &c.last_order)))
+                              K, entropic, fin, gpu_counts ? mc.data() : nullptr, &c.last_order)))
         return lz_fail(rc, "internal: candidate HSP is not on a seed hit");
     if ((rc = lz_hsps_out(fin, out, n_out))) return rc;
     { std::lock_guard<std::mutex> lk(c.counters_m); c.counters.hsps += fin.size(); }
@@ -856,10 +921,10 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
 
 // the search proper (after search_enter); with c.self.mode != LZ_SELF_OFF the count, fill and fused scan kernels drop
 // the hits a self-comparison drops
-static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
+static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out, const int8_t* match_bits = nullptr)
 {
     LzCtx& c = g_ctx;
-    SeedSearch s; s.a = a;
+    SeedSearch s; s.a = a; s.match_bits = match_bits;
     int rc;
     g_hp.start();
     if ((rc = ss_query(c, s))) return rc;
@@ -869,7 +934,7 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out)
     if ((rc = ss_plan(c, s))) return rc;
     if ((rc = ss_scan_mode(c, s))) return rc;
     if ((rc = ss_reserve(c, s))) return rc;
-    for (const LzChunk& ch : s.chunks) if ((rc = a->extend ? ss_chunk(c, s, ch) : ss_chunk_plain(c, s, ch))) return rc;
+    for (const LzChunk& ch : s.chunks) if ((rc = s.exact() ? ss_chunk_exact(c, s, ch) : a->extend ? ss_chunk(c, s, ch) : ss_chunk_plain(c, s, ch))) return rc;
     g_hp.lap(3, "chunk loop launches");
     return ss_finish(c, s, out, n_out);
 }
@@ -878,6 +943,16 @@ extern "C" int lzgpu_seed_hit_search(const lz_search_args* a, lz_hsp** out, uint
 {
     int rc = search_enter(a && out && n_out && a->sub, out, n_out);
     return rc ? rc : seed_search(a, out, n_out);
+}
+
+// Exact-match extension (lastz --exact=<length>: process_for_simple_hit with gfExtend == gfexExact, src/seed_search.c:1056-1192,
+// match_extend_seed_hit, :3018-3254).  Enumeration, the bucket streams, the tile sort and the run tables are the plain search's;
+// phase A and phase B are k_scan_exact and k_settle_exact on the match codes of both sequences (lz_exact.hpp).
+extern "C" int lzgpu_seed_hit_search_exact(const lz_search_args* a, const int8_t match_bits[256], lz_hsp** out, uint64_t* n_out)
+{
+    int rc = search_enter(a && match_bits && out && n_out, out, n_out); if (rc) return rc;
+    if (g_ctx.n_owners > 1) return LZGPU_NH_UNSUPPORTED;         // (the owner path is not tested with these kernels)
+    return seed_search(a, out, n_out, match_bits);
 }
 
 // Self-comparison (lastz --self, --band).  Every raw hit the reference drops (src/seed_search.c:841-848, 903-908,

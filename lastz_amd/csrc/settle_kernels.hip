@@ -1,6 +1,6 @@
 // settle_kernels.hip -- gfx950 kernels behind phase A (DESIGN.md section 3, rows 6, 6b and 7, and the match counts row 8's
 // host finish reads): every tile of hits sorted by partition where it lies, the runs' ranks, the bucket-serial walk with its
-// wave-cooperative X-drop extension, and the candidates' entropy inputs.
+// wave-cooperative X-drop extension, and the candidates' entropy inputs; and the walk of an exact-match search (k_settle_exact).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "lz_ctx.hpp"
@@ -8,6 +8,7 @@
 #include "lz_tile_runs.hpp"
 #include "lz_coop.hpp"
 #include "lz_seed_dev.hpp"
+#include "lz_exact.hpp"
 
 // the tiles of k_partition (lz_tile_runs.hpp: LZ_PP_TILE_HOST sizes the tile tables on the host) and the 256 partitions
 #define LZ_PP_TPB    1024                            // one workgroup per CU: 128 KiB of staging for a tile of 16384 hits (runs of 64 records per partition)
@@ -328,151 +329,9 @@ k_settle2(LzExtendParams P, const u64* __restrict__ recs, u32 n_pp_tiles, const 
     const u32 n = r1 - r0, ntiles = (n + LZ_S2_TILE - 1) / LZ_S2_TILE;
     if (ntiles == 0) return;                                    // (uniform: nothing of this partition in the chunk)
     for (u32 k = tid; k < LZ_NCLASS * LZ_NCLASS; k += LZ_S2_TPB) sh.tab[k] = score_tab_g[k];
-    for (u32 k = tid; k < LZ_S2_SORTW * LZ_NBIN; k += LZ_S2_TPB) (&sh.bm[0][0])[k] = 0ull;
-    const bool walker = w < LZ_S2_WALKW;
-    const u32 sw = w - LZ_S2_WALKW;                             // sorter wave index (sorters only)
-
-    // ---- sorter pieces
-    u64 cx[LZ_S2_ROUNDS], nx[LZ_S2_ROUNDS];                     // records of the tile to place next / to count next
-    u32 cslot[LZ_S2_ROUNDS];
-    // The partition's records lie in one run per partition tile (lz_tile_runs.hpp).  A sorter wave keeps a block of
-    // LZ_TR_BLOCK consecutive tiles' (first rank, address) of the partition, LZ_TR_K per lane (lane l: tiles cur + K l ..),
-    // that only moves forward; window_first(tt) = the first rank of the wave's window of tile tt.
-    u32 cur = 0, bf[LZ_TR_K], ba[LZ_TR_K];
-    auto load_block = [&]() {
-#pragma unroll
-        for (int j = 0; j < LZ_TR_K; j++) {
-            const u32 t = cur + lane * LZ_TR_K + (u32)j;
-            bf[j] = lz_tr_first(hist, hist_part, n_pp_tiles, t, part, r1);
-            ba[j] = t < n_pp_tiles ? run_addr[(size_t)t * LZ_NBIN + part] : 0u;
-        }
-    };
-    auto block_end = [&]() -> u32 { return (u32)__builtin_amdgcn_readlane((int)bf[LZ_TR_K - 1], 63); };
-    auto window_first = [&](u32 tt) -> u32 { return r0 + tt * (u32)LZ_S2_TILE + sw * (64u * LZ_S2_ROUNDS); };
-    // one step of the cursor ahead of load_tile(tt), where the loads have a whole placement to arrive (the usual tile
-    // needs no more than this one: 5376 ranks are about 84 partition tiles)
-    auto advance_early = [&](u32 tt) {
-        if (tt < ntiles && window_first(tt) < r1 && lz_tr_block_behind(block_end(), window_first(tt))) { cur += LZ_TR_BLOCK - 1; load_block(); }
-    };
-    auto load_tile = [&](u32 tt, u64* x) {                      // (sorters) the wave's 448 records of tile tt, 64 per round
-#pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) x[rr] = ~0ull;                                    // ~0: no record
-        const u32 g0 = window_first(tt);
-        if (tt >= ntiles || g0 >= r1) return;                   // (wave-uniform)
-        const u32 g1 = (r1 - g0 < 64u * LZ_S2_ROUNDS) ? r1 : g0 + 64u * LZ_S2_ROUNDS;
-        u8* const own = sh.own[sw];
-        u32 idx[LZ_S2_ROUNDS] = {};
-        for (;;) {
-            const u32 bend = block_end();
-            if (!lz_tr_block_behind(bend, g0)) {
-                // the runs of the block that hold ranks of the window mark their first one with 1 + their entry; a
-                // running maximum over the window then names every rank's run (k_fill_hits2's own[])
-                if (lane < 64u * LZ_S2_ROUNDS / 8u) reinterpret_cast<u64*>(own)[lane] = 0ull;
-                u32 dl[LZ_TR_K];
-#pragma unroll
-                for (int j = 0; j < LZ_TR_K; j++) {
-                    const u32 nf = j + 1 < LZ_TR_K ? bf[(j + 1) % LZ_TR_K] : (u32)__shfl_down((int)bf[0], 1);    // the next tile's first rank
-                    u32 pos;
-                    const bool m = lz_tr_mark(bf[j], nf, g0, g1, pos) && !(j == LZ_TR_K - 1 && lane == 63u);   // (the last entry only bounds the block)
-                    if (m) own[pos] = (u8)(1u + lane * LZ_TR_K + (u32)j);
-                    dl[j] = lz_tr_delta(ba[j], bf[j]);
-                }
-                const u32 bfirst = (u32)__builtin_amdgcn_readlane((int)bf[0], 0);
-                u32 carry = 0;
-#pragma unroll
-                for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
-                    const u32 g = g0 + (u32)rr * 64u + lane;
-                    const u32 mk = own[(u32)rr * 64u + lane];
-                    u32 v = mk;
-                    LZ_WAVE_SCAN_U32(v, mk, lz_umax)
-                    v = lz_umax(v, carry);
-                    carry = (u32)__builtin_amdgcn_readlane((int)v, 63);
-                    const u32 e = v - 1u;                       // (v == 0: a rank below the block, not covered)
-                    u32 d = (u32)__shfl((int)dl[0], (int)(e / LZ_TR_K));
-#pragma unroll
-                    for (int j = 1; j < LZ_TR_K; j++) { const u32 dj = (u32)__shfl((int)dl[j], (int)(e / LZ_TR_K)); if (e % LZ_TR_K == (u32)j) d = dj; }
-                    if (lz_tr_covers(g, bfirst, bend, g1)) idx[rr] = lz_tr_index(g, d);
-                }
-                if (bend >= g1) break;
-            }
-            cur += LZ_TR_BLOCK - 1; load_block();               // (a sparse partition: the window goes on in later tiles)
-        }
-#pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
-            if (g0 + (u32)rr * 64u + lane < g1) x[rr] = LZ_NT_LD(recs + (size_t)idx[rr]);
-    };
-    auto count_tile = [&](u32 tt, const u64* x, u32* slot) {    // ranks inside (wave, bucket) -> slot[], totals -> cnt[tt & 1][sw][]
-        u32* const row = sh.cnt[tt & 1u][sw];
-        reinterpret_cast<uint4*>(row)[lane] = make_uint4(0u, 0u, 0u, 0u);
-        u64* const bmr = sh.bm[sw];
-#pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
-            const bool valid = x[rr] != ~0ull;
-            const u32 b = LZ_REC_LOW8(x[rr]);
-            if (valid) atomicOr((unsigned long long*)&bmr[b], 1ull << lane);
-            const u64 peers = valid ? bmr[b] : 0ull;
-            const u32 old = valid ? row[b] : 0u;
-            const u32 rank = (u32)__popcll(peers & ((1ull << lane) - 1ull));
-            if (valid && (peers >> lane) == 1ull) { row[b] = old + (u32)__popcll(peers); bmr[b] = 0ull; }   // the highest peer
-            slot[rr] = old + rank;
-        }
-    };
-    auto place_tile = [&](u32 tt, const u64* x, const u32* slot) {
-        // bucket bases of the tile: every sorter wave sums the 12 rows for its own use (lane l: buckets 4l .. 4l+3)
-        const u32 (*cn)[LZ_NBIN] = sh.cnt[tt & 1u];
-        uint4 tot = make_uint4(0u, 0u, 0u, 0u), pre = tot;
-#pragma unroll
-        for (u32 k = 0; k < LZ_S2_SORTW; k++) {
-            const uint4 v = reinterpret_cast<const uint4*>(cn[k])[lane];
-            if (k == sw) pre = tot;
-            tot.x += v.x; tot.y += v.y; tot.z += v.z; tot.w += v.w;
-        }
-        const u32 mine = tot.x + tot.y + tot.z + tot.w;
-        u32 inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d); if ((int)lane >= d) inc += t; }
-        const u32 b0 = inc - mine, b1 = b0 + tot.x, b2 = b1 + tot.y, b3 = b2 + tot.z;
-        reinterpret_cast<uint4*>(sh.woff[sw])[lane] = make_uint4(b0 + pre.x, b1 + pre.y, b2 + pre.z, b3 + pre.w);
-        if (sw == 0) {
-            reinterpret_cast<uint4*>(sh.lbeg[tt & 1u])[lane] = make_uint4(b0, b1, b2, b3);
-            reinterpret_cast<uint4*>(sh.lcnt[tt & 1u])[lane] = tot;
-        }
-        u64* const dst = sh.rec[tt & 1u];
-#pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
-            if (x[rr] != ~0ull) dst[sh.woff[sw][LZ_REC_LOW8(x[rr])] + slot[rr]] = x[rr];
-    };
-
-    // ---- the two roles run their own loops (the register allocator sees two disjoint sets of live values) and
-    // meet at the same barriers: 3 in the prologue, one per tile.  (s_barrier counts arrivals per wave, not places.)
-    __syncthreads();                                            // tab, bm
-    if (!walker) {
-        // prologue: tile 0 counted | tile 0 placed, tile 1 counted | then per interval t: tile t+1 placed, tile t+2 counted
-        load_block();
-        load_tile(0, cx); load_tile(1, nx); count_tile(0, cx, cslot);
-        __syncthreads();
-        place_tile(0, cx, cslot);
-#pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) cx[rr] = nx[rr];
-        load_tile(2, nx);
-        count_tile(1, cx, cslot);
-        __syncthreads();
-        for (u32 t = 0; t < ntiles; t++) {
-            LZ_S2_CLK_BEGIN(sw == 0 && lane == 0);
-            advance_early(t + 3);
-            if (t + 1 < ntiles) place_tile(t + 1, cx, cslot);
-#pragma unroll
-            for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) cx[rr] = nx[rr];
-            load_tile(t + 3, nx);                               // (past the last tile: no loads, "no record")
-            if (t + 2 < ntiles) count_tile(t + 2, cx, cslot);
-            LZ_S2_CLK_MID(sw == 0 && lane == 0, 2);
-            __syncthreads();
-            LZ_S2_CLK_END(sw == 0 && lane == 0, 3);
-        }
-        return;
-    }
-    __syncthreads();
-    __syncthreads();
+    // the sorter waves: tile-run gather, count and placement of tiles into sh.rec / sh.lbeg / sh.lcnt, up to the barriers at
+    // which the walkers take over tile 0 (text shared with k_settle_exact; the sorters return inside it)
+#include "lz_settle_sorters.inc"
     constexpr u32 BPW = LZ_NBIN / LZ_S2_WALKW;                   // buckets (= walking lanes) per walking wave
     const bool wl = lane < BPW;
     const u32 bucket = (w * BPW + lane) & (LZ_NBIN - 1);        // the lane's bucket
@@ -570,6 +429,106 @@ int lzk_settle(LzCtx& c, const LzExtendParams& P, u64 n, u32 out_cap)
     hipLaunchKernelGGL(k_settle2, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), c.stream, P, c.keys.as<u64>(), n_pp_tiles,
                        c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(),
                        c.diag_end.as<u32>(), c.score_tab.as<s32>(), c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap, c.dev_counters.as<u64>());
+    c.timer.end(c.stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Phase B of an exact-match search (lastz --exact, lz_exact.hpp): k_settle2's sorters and one walking lane per bucket with
+// diagEnd in a register.  A fast record is the drop test and dend = max(dend, extent); a SLOW record that passes the drop
+// test is extended by the lane's whole wave against the real dend, 64 x 32 bases per step and side (a ballot finds the
+// first block that ends the run: a run of megabases takes a few hundred steps).  No scores, no class table (sh.tab stays unused).
+__global__ void __launch_bounds__(LZ_S2_TPB)
+k_settle_exact(LzExactParams P, const u64* __restrict__ recs, u32 n_pp_tiles, const u32* __restrict__ hist, const u32* __restrict__ hist_part,
+               const u32* __restrict__ run_addr, const u32* __restrict__ bin_base, u32* __restrict__ diag_end,
+               LzHspRec* __restrict__ out, u32* __restrict__ out_count, u32 out_cap)
+{
+    extern __shared__ __align__(16) unsigned char lz_s2_smem[];
+    LzSettle2Shared& sh = *reinterpret_cast<LzSettle2Shared*>(lz_s2_smem);
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it
+    const u32 part = blockIdx.x;
+    const u32 r0 = bin_base[part], r1 = bin_base[part + 1];
+    const u32 n = r1 - r0, ntiles = (n + LZ_S2_TILE - 1) / LZ_S2_TILE;
+    if (ntiles == 0) return;                                    // (uniform: nothing of this partition in the chunk)
+#include "lz_settle_sorters.inc"
+    constexpr u32 BPW = LZ_NBIN / LZ_S2_WALKW;                   // buckets (= walking lanes) per walking wave
+    const bool wl = lane < BPW;
+    const u32 bucket = (w * BPW + lane) & (LZ_NBIN - 1);        // the lane's bucket
+    const u32 h = part * LZ_NBIN + bucket;
+    const u32 L = P.seed_len;
+    u32 dend = wl ? diag_end[h] : 0u;
+    for (u32 t = 0; t < ntiles; t++) {
+        const u64* const rec = sh.rec[t & 1u];
+        u32 p = wl ? sh.lbeg[t & 1u][bucket] : 0u; const u32 end = wl ? p + sh.lcnt[t & 1u][bucket] : 0u;
+        for (;;) {
+            // every lane settles records from their phase-A summaries, LZ_ST_BATCH at a time, until one needs an extension
+            bool pending = false; u32 pp2 = 0, ppay = 0;
+            while (__ballot(p < end && !pending)) {
+                u64 r[LZ_ST_BATCH];
+#pragma unroll
+                for (int k = 0; k < LZ_ST_BATCH; k++) r[k] = rec[p + k];                // (reads past `end` stay inside rec[] and are not used)
+                bool live = !pending;
+                u32 np = 0;
+#pragma unroll
+                for (int k = 0; k < LZ_ST_BATCH; k++) {
+                    const u32 p2 = LZ_REC_POS2(r[k]), pay = LZ_REC_PAYLOAD(r[k]);
+                    const bool in = live && (p + (u32)k < end);
+                    const bool drop = lz_exact_drops(dend, p2, L);
+                    const bool slow = LZ_REC_SLOW(r[k]) != 0 && !drop;
+                    const bool go = in && !slow;                               // the record is consumed here
+                    dend = (go && !drop) ? lz_exact_fast_dend(dend, p2, L, pay) : dend;
+                    np += go ? 1u : 0u;
+                    if (in && slow) { pending = true; pp2 = p2; ppay = pay; }
+                    live = go;
+                }
+                p += np;
+            }
+            u64 mask = __ballot(pending);
+            if (!mask) break;
+            while (mask) {                                      // the wave extends the pending hits, one at a time
+                const int src = (int)__ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const u32 sp2 = (u32)__shfl((int)pp2, src), spay = (u32)__shfl((int)ppay, src), sdend = (u32)__shfl((int)dend, src);
+                const u32 pos1 = sp2 + ((spay << 16) | (part * LZ_NBIN + w * BPW + (u32)src));
+                const u32 room = sp2 - L - sdend;
+                u32 right = 0, left = 0;
+                for (u32 b = lane;; b += 64u) {                 // (b - lane is wave-uniform; a block past the sequences returns 0: the loop ends)
+                    const u32 run = lz_exact_block_right(P, pos1, sp2, b);
+                    const u64 stop = __ballot(run < LZ_EX_W);
+                    if (stop) { const int f = (int)__ffsll((long long)stop) - 1; right = (b - lane + (u32)f) * LZ_EX_W + (u32)__shfl((int)run, f); break; }
+                }
+                for (u32 b = lane;; b += 64u) {                 // (a block past the room returns 0)
+                    const u32 run = lz_exact_block_left(P, pos1, sp2, room, b);
+                    const u64 stop = __ballot(run < LZ_EX_W);
+                    if (stop) { const int f = (int)__ffsll((long long)stop) - 1; left = (b - lane + (u32)f) * LZ_EX_W + (u32)__shfl((int)run, f); break; }
+                }
+                if ((int)lane == src) {
+                    LzHspRec o;
+                    if (lz_exact_finish(P, pos1, sp2, dend, left, right, o)) {
+                        const u32 oslot = atomicAdd(out_count, 1u);
+                        if (oslot < out_cap) out[oslot] = o;
+                    }
+                    p++;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (wl) diag_end[h] = dend;
+}
+
+// phase B of an exact-match search on the chunk's n records in c.keys: as lzk_settle, without counters
+int lzk_settle_exact(LzCtx& c, const LzExactParams& P, u64 n, u32 out_cap)
+{
+    if (n == 0) return 0;
+    const u32 n_pp_tiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
+    c.timer.begin("k_settle_exact", c.stream);
+    if (!c.settle_exact_attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_settle_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzSettle2Shared))); c.settle_exact_attr_set = true; }
+    hipLaunchKernelGGL(k_settle_exact, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), c.stream, P, c.keys.as<u64>(), n_pp_tiles,
+                       c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(),
+                       c.diag_end.as<u32>(), c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap);
     c.timer.end(c.stream);
     LZ_HIP(hipGetLastError());
     return 0;

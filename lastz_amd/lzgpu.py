@@ -76,7 +76,7 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
            "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_table_num_words",
            "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_table_limit", "lzgpu_table_find_limit", "lzgpu_table_count_distribution", "lzgpu_device_copy",
-           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
+           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_seed_hit_search_exact", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
            "lzgpu_set_bucket_owner", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
@@ -111,6 +111,7 @@ class Lib:
         if prefix == "lzgpu_":
             self.L.lzgpu_seed_hit_search_self.argtypes = [C.POINTER(SearchArgs), C.POINTER(SelfArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
             self.L.lzgpu_seed_hit_search_within.argtypes = [C.POINTER(SearchArgs), C.POINTER(PosFilter), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+            self.L.lzgpu_seed_hit_search_exact.argtypes = [C.POINTER(SearchArgs), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         f("table_prepare").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(SeedDesc), C.c_uint32]
         f("set_hit_capacity").argtypes = [C.c_uint64]
@@ -275,6 +276,28 @@ class Lib:
         q_interval of the query (hp->targetInterval / hp->queryInterval, origin-0 half-open); the extension is not limited"""
         w = PosFilter(t_interval[0], t_interval[1], q_interval[0], q_interval[1])
         return self._search(w, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end)
+
+    def seed_hit_search_exact(self, match_bits, length, q=None, slot=-1, start=0, end=0):
+        """lastz --exact=<length>: the seed hits extended while bases match (match_bits = hp->charToBits, nuc_to_bits: lower
+        case matches upper case, everything else matches nothing); HSPs of at least `length` bases, score == length"""
+        a = SearchArgs()
+        mb = np.ascontiguousarray(match_bits, dtype=np.int8)
+        assert len(mb) == 256
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.uint8)
+            a.query, a.qlen = q.ctypes.data, len(q)
+        else:
+            a.query, a.qlen = None, self._keep[("qlen", slot)]
+        a.query_slot, a.start, a.end = slot, start, end
+        a.sub, a.hsp_threshold = None, length
+        out = C.c_void_p()
+        n = C.c_uint64()
+        self._check(self.L.lzgpu_seed_hit_search_exact(C.byref(a), _ptr(mb), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search_exact")
+        res = np.zeros(n.value, dtype=HSP_DTYPE)
+        if n.value:
+            C.memmove(_ptr(res), out, n.value * HSP_DTYPE.itemsize)
+        self.L.lzgpu_free(out)
+        return res
 
     def _search(self, self_args, sub, q, slot, xdrop, hsp_threshold, entropic, extend, start, end):
         a = SearchArgs()
