@@ -255,6 +255,24 @@ int lzgpu_seed_hit_search_within(const lz_search_args* args, const lz_pos_filter
  * return LZGPU_NH_HSP_OVERFLOW.  Not combined with a self-comparison or a position filter. */
 int lzgpu_seed_hit_search_exact(const lz_search_args* args, const int8_t match_bits[256], lz_hsp** out, uint64_t* n_out);
 
+/* ---- B2 with N-mismatch extension (lastz --mismatch=<count>,<length>, --<count>mismatch=<length>) --------------------
+ * seed_hit_search for processor == process_for_simple_hit with gfExtend in gfexMismatch_min..gfexMismatch_max
+ * (src/seed_search.c:1056-1192): per raw hit in discovery order the diagEnd test (:1113), then mismatch_extend_seed_hit
+ * (:3450-3778) with M = max_mismatches.  The seed window is read right to left and its mismatches counted (E); at the
+ * (M+1)-th, at query position m, the hit yields no HSP and diagEnd = max(diagEnd, m) (:3512-3525, :3754-3777).  Otherwise
+ * the left scan collects up to M+1-E mismatch positions, stopping early at max(diagEnd, start of either sequence) or at a
+ * NUL, where the stop is one more interval start (:3545-3608); every further mismatch to the right -- after as many as the
+ * left scan fell short of (:3651-3656) -- closes the interval that opens at the next start, leftmost first, and a NUL or the
+ * end of either sequence closes the current one (:3634-3686); the longest interval wins, the leftmost among equals.  It is an
+ * HSP iff length >= (unsigned) hsp_threshold (:3733), reported with the positions of its right end and score == length; then
+ * diagEnd = max(diagEnd, its right bounding mismatch + 1) (:3703-3711), otherwise the leftmost mismatch of the window, or
+ * without one the first mismatch or stop right of it (:3521, :3649-3650).
+ * A mismatch is what lzgpu_seed_hit_search_exact calls one (match_bits = hp->charToBits; N against N mismatches, and so does a
+ * NUL, :3585, :3641).  max_mismatches outside 1..50 or hsp_threshold < 1 return LZGPU_ERR_ARG.  Everything else -- the args
+ * read, the order, the counters, bucket owners, the HSP capacity, what it is not combined with -- is as in
+ * lzgpu_seed_hit_search_exact. */
+int lzgpu_seed_hit_search_mismatch(const lz_search_args* args, const int8_t match_bits[256], int32_t max_mismatches, lz_hsp** out, uint64_t* n_out);
+
 /* ---- B1 + B2 for many small rectangles of the two sequences at once ----------------------------
  * What src/tweener.c:769-829 (bounded_align) does for every in-between window of `lastz --inner=<score>`:
  * build_seed_position_table on target[t_off, t_off + t_len) with the inner seed, seed_hit_search of

@@ -553,7 +553,8 @@ u64 seed_hit_search
 	lz_hsp*        h = NULL;
 	uint64_t       n = 0, k;
 	u64            basesHit = 0;
-	int            rc;
+	int            rc, mismatchExtend;
+	char*          mmEnv;
 
 	if (twMode == twRecord)                                     /* a window of the tweener: noted, searched later with all the others */
 		{
@@ -582,6 +583,9 @@ u64 seed_hit_search
 		}
 
 	clock_mark ("search", "called");
+	/* --mismatch=<count>,<length> goes to the device only under LZGPU_MISMATCH=1: the default stays the reference's routine */
+	mismatchExtend = (processor == process_for_simple_hit) && (hp->gfExtend >= gfexMismatch_min) && (hp->gfExtend <= gfexMismatch_max)
+	              && ((mmEnv = getenv ("LZGPU_MISMATCH")) != NULL) && (mmEnv[0] == '1') && (mmEnv[1] == 0);
 	/* one process per GPU: a unit of another rank yields nothing here, whichever routine would have searched it
 	 * (the tweener's windows are cut from a unit this rank owns: src/tweener.c:1073-1075 gives them no file) */
 	if (seq2->fileType != seq_type_nofile)
@@ -592,8 +596,8 @@ u64 seed_hit_search
 		}
 
 	if ((pt != devTable) || (devTable == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
-	 || (processor != process_for_simple_hit) || ((hp->gfExtend != gfexXDrop) && (hp->gfExtend != gfexExact))
-	 || ((hp->gfExtend == gfexExact) && ((selfCompare) || (hp->posFilter) || (bandWidth != 0)))   /* --exact: alone, not with --self, --chores or --band */
+	 || (processor != process_for_simple_hit) || ((hp->gfExtend != gfexXDrop) && (hp->gfExtend != gfexExact) && (!mismatchExtend))
+	 || (((hp->gfExtend == gfexExact) || (mismatchExtend)) && ((selfCompare) || (hp->posFilter) || (bandWidth != 0)))   /* --exact, --mismatch: alone, not with --self, --chores or --band */
 	 || (hp->hspThreshold.t != 'S') || ((hp->posFilter) && (selfCompare)) || (hp->minMatches >= 0) || (hp->reportEntropy)
 	 || ((!selfCompare) && (bandWidth != 0)) || (searchLimit != 0)
 	 || (seq2->fileType == seq_type_qdna) || (hp->seq1 != seq1) || (hp->seq2 != seq2)
@@ -614,6 +618,11 @@ u64 seed_hit_search
 		{
 		rc = lzgpu_seed_hit_search_exact (&a, (const int8_t*) hp->charToBits, &h, &n);
 		if (rc < 0) suicidef ("lzgpu_seed_hit_search_exact: %s", lzgpu_last_error());
+		}
+	else if (mismatchExtend)                                    /* --mismatch=<count>,<length>: mismatch_extend_seed_hit (src/seed_search.c:3450-3778) on the device, likewise */
+		{
+		rc = lzgpu_seed_hit_search_mismatch (&a, (const int8_t*) hp->charToBits, (int32_t) hp->gfExtend, &h, &n);
+		if (rc < 0) suicidef ("lzgpu_seed_hit_search_mismatch: %s", lzgpu_last_error());
 		}
 	else if (selfCompare)                                       /* --self (and --band): the hits seed_hit_below_diagonal drops, dropped on the device */
 		{

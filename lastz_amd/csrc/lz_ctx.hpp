@@ -133,6 +133,7 @@ struct LzCtx {
     bool win_attr_set = false;        // k_window_search's dynamic-LDS attribute has been set on this device context (lzgpu_shutdown clears it)
     bool settle_attr_set = false;     // likewise k_settle2's
     bool settle_exact_attr_set = false;   // likewise k_settle_exact's
+    bool settle_mismatch_attr_set = false;   // ... and k_settle_mismatch's
     u64 dp_longest[4] = { 0, 0, 0, 0 };   // lzgpu_dp_longest: rows, cells, sweep and traceback ticks of the DP that swept the most rows since the last reset
     // the two settings below keep their value across shutdown + init, as hit_capacity does
     u32 dp_slot_tb = 8u << 20;        // lzgpu_set_dp_slot: the uniform traceback slot (bytes) per DP
@@ -171,7 +172,7 @@ struct LzCtx {
         pinned = nullptr; pinned_words = 0;
         have_table = false; wctx_gen = 0; wctx_code_key = 0; limit = 0; full_num_words = 0;
         score_sub.clear(); lut_m4.clear(); lut_xdrop = -1;
-        win_attr_set = false; settle_attr_set = false; settle_exact_attr_set = false;
+        win_attr_set = false; settle_attr_set = false; settle_exact_attr_set = false; settle_mismatch_attr_set = false;
     }
 };
 
@@ -183,7 +184,7 @@ int lz_fail(int code, const char* fmt, ...);
 
 // ---- the seed stage's launchers: all asynchronous on c.stream (lzk_encode: or the stream it is given).  A launcher is passed what
 // varies per call -- the chunk, the kernels' parameters, the mode -- and reads the buffers that are members of LzCtx from c. ----
-struct LzChunk; struct LzLutParams; struct LzExactParams;     // lz_host.hpp, lz_lut.hpp, lz_exact.hpp
+struct LzChunk; struct LzLutParams; struct LzExactParams; struct LzMismatchParams;     // lz_host.hpp, lz_lut.hpp, lz_exact.hpp
 #include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
 // seq_kernels.hip
 int lzk_encode(LzCtx& c, const u8* raw, u8* code, u32 len, const u8* cls256_dev, hipStream_t st = nullptr, KernelTimer* timer = nullptr);   // defaults: c.stream, c.timer
@@ -215,5 +216,8 @@ int lzk_hist_scan(LzCtx& c, u64 n);                  // after the partition of t
 int lzk_settle(LzCtx& c, const LzExtendParams& P, u64 n, u32 out_cap);   // -> c.diag_end, c.hsp_out / c.hsp_count, c.dev_counters
 int lzk_hsp_match_counts(LzCtx& c, u32 n_rec, const SeqSlot& q);         // -> c.hsp_mc
 int lzk_settle_exact(LzCtx& c, const LzExactParams& P, u64 n, u32 out_cap);   // phase B of an exact-match search -> c.diag_end, c.hsp_out / c.hsp_count
+int lzk_settle_mismatch(LzCtx& c, const LzMismatchParams& P, u64 n, u32 out_cap);   // phase B of an N-mismatch search, likewise
 // exact_kernels.hip
 int lzk_scan_exact(LzCtx& c, const LzExactParams& P, u64 n);             // phase A of an exact-match search: c.keys -> c.summ (sized by the caller)
+// mismatch_kernels.hip
+int lzk_scan_mismatch(LzCtx& c, const LzMismatchParams& P, u64 n);       // phase A of an N-mismatch search, likewise

@@ -17,6 +17,7 @@
 #include "lz_host.hpp"
 #include "lz_lut.hpp"
 #include "lz_exact.hpp"
+#include "lz_mismatch.hpp"
 
 // ------------------------------------------------------------------------------ context
 
@@ -643,9 +644,10 @@ struct SeedSearch {                                             // a seed_search
     std::vector<LzChunk> chunks; u64 max_chunk = 0;             // [i0,i1) in query positions with at most hit_capacity hits each
     int mode = 2; bool fused = false;                           // phase-A scan mode; k_scan_hits2 in the place of fill + scan
     const int8_t* match_bits = nullptr;                         // an exact-match search (lzgpu_seed_hit_search_exact): a->sub, xdrop, entropic and extend are not read
+    u32 mismatches = 0;                                         // ... or, not 0, an N-mismatch search (lzgpu_seed_hit_search_mismatch), on the same match codes
     bool exact() const { return match_bits != nullptr; }
     bool extend() const { return exact() || a->extend != 0; }
-    LzExtendParams P; LzLutParams Q; LzExactParams X;
+    LzExtendParams P; LzLutParams Q; LzExactParams X; LzMismatchParams MM;
     u32 out_cap = 0;
     std::vector<lz_hsp> plain;                                  // !a->extend: every hit
 };
@@ -775,6 +777,7 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
         LzExactParams& X = s.X;
         X.t2 = c.target.mtwo.as<u8>(); X.tsp = c.target.mspc.as<u8>(); X.q2 = qs->mtwo.as<u8>(); X.qsp = qs->mspc.as<u8>();
         X.tlen = c.geom.tlen; X.qlen = qs->len; X.seed_len = s.L; X.thr = (u32)a->hsp_threshold;      // src/seed_search.c:3209
+        s.MM.X = X; s.MM.traw = c.target.raw_base(); s.MM.qraw = qs->raw_base(); s.MM.M = s.mismatches;      // (the bytes k_hsp_match_counts reads, too)
         s.fused = false;
         return 0;
     }
@@ -854,15 +857,16 @@ static int ss_chunk(LzCtx& c, SeedSearch& s, const LzChunk& ch)
     if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
     return lzk_settle(c, s.P, ch.nh, s.out_cap);
 }
-// ... of an exact-match search: k_scan_exact and k_settle_exact in the places of the X-drop kernels, everything between them as it is
+// ... of an exact-match search: k_scan_exact and k_settle_exact in the places of the X-drop kernels, everything between them as it is;
+// of an N-mismatch search: k_scan_mismatch and k_settle_mismatch there
 static int ss_chunk_exact(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
     int rc;
     if ((rc = lzk_fill_hits(c, s.lo, ch, s.n))) return rc;
-    if ((rc = lzk_scan_exact(c, s.X, ch.nh))) return rc;
+    if ((rc = s.mismatches ? lzk_scan_mismatch(c, s.MM, ch.nh) : lzk_scan_exact(c, s.X, ch.nh))) return rc;
     if ((rc = lzk_partition(c, false, ch.nh))) return rc;
     if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
-    return lzk_settle_exact(c, s.X, ch.nh, s.out_cap);
+    return s.mismatches ? lzk_settle_mismatch(c, s.MM, ch.nh, s.out_cap) : lzk_settle_exact(c, s.X, ch.nh, s.out_cap);
 }
 // ... of a search without extension (process_for_plain_hit): every hit is reported
 static int ss_chunk_plain(LzCtx& c, SeedSearch& s, const LzChunk& ch)
@@ -921,10 +925,10 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
 
 // the search proper (after search_enter); with c.self.mode != LZ_SELF_OFF the count, fill and fused scan kernels drop
 // the hits a self-comparison drops
-static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out, const int8_t* match_bits = nullptr)
+static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out, const int8_t* match_bits = nullptr, u32 mismatches = 0)
 {
     LzCtx& c = g_ctx;
-    SeedSearch s; s.a = a; s.match_bits = match_bits;
+    SeedSearch s; s.a = a; s.match_bits = match_bits; s.mismatches = mismatches;
     int rc;
     g_hp.start();
     if ((rc = ss_query(c, s))) return rc;
@@ -953,6 +957,18 @@ extern "C" int lzgpu_seed_hit_search_exact(const lz_search_args* a, const int8_t
     int rc = search_enter(a && match_bits && out && n_out, out, n_out); if (rc) return rc;
     if (g_ctx.n_owners > 1) return LZGPU_NH_UNSUPPORTED;         // (the owner path is not tested with these kernels)
     return seed_search(a, out, n_out, match_bits);
+}
+
+// N-mismatch extension (lastz --mismatch=<count>,<length>: process_for_simple_hit with gfExtend in gfexMismatch_min..gfexMismatch_max,
+// src/seed_search.c:1056-1192, mismatch_extend_seed_hit, :3450-3778).  As the exact-match search, on the same match codes, with
+// k_scan_mismatch and k_settle_mismatch (lz_mismatch.hpp); a->hsp_threshold is the length (:3703).
+extern "C" int lzgpu_seed_hit_search_mismatch(const lz_search_args* a, const int8_t match_bits[256], int32_t max_mismatches, lz_hsp** out, uint64_t* n_out)
+{
+    int rc = search_enter(a && match_bits && out && n_out, out, n_out); if (rc) return rc;
+    if (max_mismatches < 1 || max_mismatches > (int32_t)LZ_MM_MAX) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search_mismatch(), %d mismatches (1..%u)", (int)max_mismatches, LZ_MM_MAX);
+    if (a->hsp_threshold < 1) return lz_fail(LZGPU_ERR_ARG, "in seed_hit_search_mismatch(), length %d", (int)a->hsp_threshold);
+    if (g_ctx.n_owners > 1) return LZGPU_NH_UNSUPPORTED;         // (as lzgpu_seed_hit_search_exact)
+    return seed_search(a, out, n_out, match_bits, (u32)max_mismatches);
 }
 
 // Self-comparison (lastz --self, --band).  Every raw hit the reference drops (src/seed_search.c:841-848, 903-908,

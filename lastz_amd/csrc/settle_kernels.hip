@@ -9,6 +9,7 @@
 #include "lz_coop.hpp"
 #include "lz_seed_dev.hpp"
 #include "lz_exact.hpp"
+#include "lz_mismatch.hpp"
 
 // the tiles of k_partition (lz_tile_runs.hpp: LZ_PP_TILE_HOST sizes the tile tables on the host) and the 256 partitions
 #define LZ_PP_TPB    1024                            // one workgroup per CU: 128 KiB of staging for a tile of 16384 hits (runs of 64 records per partition)
@@ -527,6 +528,149 @@ int lzk_settle_exact(LzCtx& c, const LzExactParams& P, u64 n, u32 out_cap)
     c.timer.begin("k_settle_exact", c.stream);
     if (!c.settle_exact_attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_settle_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzSettle2Shared))); c.settle_exact_attr_set = true; }
     hipLaunchKernelGGL(k_settle_exact, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), c.stream, P, c.keys.as<u64>(), n_pp_tiles,
+                       c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(),
+                       c.diag_end.as<u32>(), c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap);
+    c.timer.end(c.stream);
+    LZ_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Phase B of an N-mismatch search (lastz --mismatch, lz_mismatch.hpp): k_settle_exact's frame -- k_settle2's sorters, one walking
+// lane per bucket with diagEnd in a register, a fast record is the drop test and dend = max(dend, extent).  A SLOW record that
+// passes the drop test is extended by the lane's whole wave against the real dend: per step and side 64 x 32 bases, a wave
+// prefix sum of the mismatch words' popcounts says which lane's bits are the next of the K = M + 1 - E wanted positions, which
+// go to the wave's two lists in LDS (sh.tab's place: no class table here); lane j then asks whether position j is a stop,
+// evaluates the pairing of right mismatch j, and a wave reduction takes the longest, the earliest among equals.  An identical
+// megabase takes a few hundred steps per side.
+__device__ __forceinline__ void lz_mm_wave_lds_sync()           // the wave's own LDS stores before its other lanes' loads
+{ __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+// the first K mismatch positions of one side in scan order -> list[0..K) (every argument wave-uniform).  Positions are s32: the
+// loop goes at most one step (2048 bases, + one block) past the scan's reach, so they stay in range as long as both sequences are
+// shorter than 2^31 - 2080 bases (the library takes sequences below 2^31; an entry beyond a stop is never used in any case: the
+// first stop ends its list)
+template <bool RIGHT>
+__device__ __forceinline__ void lz_mm_wave_collect(const LzMismatchParams& P, const LzMmHit& H, u32 K, u32 lane, volatile s32* list)
+{
+    u32 have = 0;
+    for (u32 b0 = 0; have < K; b0 += 64u) {                     // (a block beyond the scan's reach is 32 mismatches: the loop ends)
+        u32 wd = RIGHT ? lz_mm_block_right(P, H, b0 + lane) : lz_mm_block_left(P, H, b0 + lane);
+        const u32 cnt = lz_mm_popc(wd);
+        u32 inc = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const u32 t = __shfl_up(inc, d); if ((int)lane >= d) inc += t; }
+        u32 at = have + inc - cnt;
+        const s32 base = RIGHT ? (s32)((s64)H.pos2 + (s64)LZ_EX_W * (s64)(b0 + lane))
+                               : (s32)((s64)H.pos2 - (s64)P.X.seed_len - (s64)LZ_EX_W * (s64)(b0 + lane)) - 1;
+        for (; wd && at < K; wd &= wd - 1u) { const s32 k = (s32)__builtin_ctz(wd); list[at++] = RIGHT ? base + k : base - k; }
+        have += (u32)__shfl((int)inc, 63);
+    }
+    lz_mm_wave_lds_sync();
+}
+static_assert(LZ_S2_WALKW * 2 * LZ_MM_LIST <= LZ_NCLASS * LZ_NCLASS && LZ_MM_MAX + 1 <= LZ_MM_LIST, "the walking waves' lists lie in sh.tab");
+__global__ void __launch_bounds__(LZ_S2_TPB)
+k_settle_mismatch(LzMismatchParams P, const u64* __restrict__ recs, u32 n_pp_tiles, const u32* __restrict__ hist, const u32* __restrict__ hist_part,
+                  const u32* __restrict__ run_addr, const u32* __restrict__ bin_base, u32* __restrict__ diag_end,
+                  LzHspRec* __restrict__ out, u32* __restrict__ out_count, u32 out_cap)
+{
+    extern __shared__ __align__(16) unsigned char lz_s2_smem[];
+    LzSettle2Shared& sh = *reinterpret_cast<LzSettle2Shared*>(lz_s2_smem);
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform, and the compiler knows it
+    const u32 part = blockIdx.x;
+    const u32 r0 = bin_base[part], r1 = bin_base[part + 1];
+    const u32 n = r1 - r0, ntiles = (n + LZ_S2_TILE - 1) / LZ_S2_TILE;
+    if (ntiles == 0) return;                                    // (uniform: nothing of this partition in the chunk)
+#include "lz_settle_sorters.inc"
+    constexpr u32 BPW = LZ_NBIN / LZ_S2_WALKW;                   // buckets (= walking lanes) per walking wave
+    const bool wl = lane < BPW;
+    const u32 bucket = (w * BPW + lane) & (LZ_NBIN - 1);        // the lane's bucket
+    const u32 h = part * LZ_NBIN + bucket;
+    const u32 L = P.X.seed_len;
+    volatile s32* const sl = sh.tab + (w & (LZ_S2_WALKW - 1u)) * (2u * LZ_MM_LIST);      // the wave's starts, nearest first
+    volatile s32* const rl = sl + LZ_MM_LIST;                                            // ... and its right mismatches
+    u32 dend = wl ? diag_end[h] : 0u;
+    for (u32 t = 0; t < ntiles; t++) {
+        const u64* const rec = sh.rec[t & 1u];
+        u32 p = wl ? sh.lbeg[t & 1u][bucket] : 0u; const u32 end = wl ? p + sh.lcnt[t & 1u][bucket] : 0u;
+        for (;;) {
+            // every lane settles records from their phase-A summaries, LZ_ST_BATCH at a time, until one needs an extension
+            bool pending = false; u32 pp2 = 0, ppay = 0;
+            while (__ballot(p < end && !pending)) {
+                u64 r[LZ_ST_BATCH];
+#pragma unroll
+                for (int k = 0; k < LZ_ST_BATCH; k++) r[k] = rec[p + k];                // (reads past `end` stay inside rec[] and are not used)
+                bool live = !pending;
+                u32 np = 0;
+#pragma unroll
+                for (int k = 0; k < LZ_ST_BATCH; k++) {
+                    const u32 p2 = LZ_REC_POS2(r[k]), pay = LZ_REC_PAYLOAD(r[k]);
+                    const bool in = live && (p + (u32)k < end);
+                    const bool drop = lz_exact_drops(dend, p2, L);
+                    const bool slow = LZ_REC_SLOW(r[k]) != 0 && !drop;
+                    const bool go = in && !slow;                               // the record is consumed here
+                    dend = (go && !drop) ? lz_exact_fast_dend(dend, p2, L, pay) : dend;
+                    np += go ? 1u : 0u;
+                    if (in && slow) { pending = true; pp2 = p2; ppay = pay; }
+                    live = go;
+                }
+                p += np;
+            }
+            u64 mask = __ballot(pending);
+            if (!mask) break;
+            while (mask) {                                      // the wave extends the pending hits, one at a time
+                const int src = (int)__ffsll((long long)mask) - 1;
+                mask &= mask - 1;
+                const u32 sp2 = (u32)__shfl((int)pp2, src), spay = (u32)__shfl((int)ppay, src), sdend = (u32)__shfl((int)dend, src);
+                const u32 pos1 = sp2 + ((spay << 16) | (part * LZ_NBIN + w * BPW + (u32)src));
+                const LzMmHit H = lz_mm_hit(P, pos1, sp2, sdend);
+                const u32 K = P.M + 1u - H.E;                   // (a SLOW record has E <= M)
+                // the starts: the first stop among them ends the list
+                lz_mm_wave_collect<false>(P, H, K, lane, sl);
+                const s32 mine_l = lane < K ? sl[lane] : 0;
+                const u64 hard_l = __ballot(lane < K && lz_mm_hard_left(P, H, mine_l));
+                const u32 c = hard_l ? (u32)__ffsll((long long)hard_l) : K;
+                if (hard_l && lane + 1u == c) sl[lane] = lz_mm_stop_start(H, mine_l);
+                // the right mismatches, likewise
+                lz_mm_wave_collect<true>(P, H, K, lane, rl);      // (its LDS synchronisation covers the store above)
+                const s32 mine_r = lane < K ? rl[lane] : 0;
+                const u64 hard_r = __ballot(lane < K && lz_mm_hard_right(P, H, mine_r));
+                const u32 nr = hard_r ? (u32)__ffsll((long long)hard_r) : K;
+                // lane j: the interval right mismatch j closes
+                u64 key = 0;
+                if (lane < nr) {
+                    const int at = lz_mm_pair_start(lane, hard_r != 0 && lane + 1u == nr, c, K);
+                    if (at >= 0) key = lz_mm_pair_key((u32)(mine_r - sl[at]), lane);
+                }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) { const u64 o = (u64)__shfl_xor((unsigned long long)key, d); if (o > key) key = o; }
+                const u32 jbest = 255u - (u32)(key & 0xFFu);
+                const s32 right = __shfl(mine_r, (int)jbest), first_right = __shfl(mine_r, 0);
+                const s32 left = right - (s32)(u32)(key >> 8);
+                if ((int)lane == src) {
+                    LzHspRec o;
+                    if (lz_mm_finish(P, H, dend, left, right, first_right, o)) {
+                        const u32 oslot = atomicAdd(out_count, 1u);
+                        if (oslot < out_cap) out[oslot] = o;
+                    }
+                    p++;
+                }
+                lz_mm_wave_lds_sync();                          // (the lists are free again)
+            }
+        }
+        __syncthreads();
+    }
+    if (wl) diag_end[h] = dend;
+}
+
+// phase B of an N-mismatch search on the chunk's n records in c.keys: as lzk_settle_exact
+int lzk_settle_mismatch(LzCtx& c, const LzMismatchParams& P, u64 n, u32 out_cap)
+{
+    if (n == 0) return 0;
+    const u32 n_pp_tiles = (u32)((n + LZ_PP_TILE - 1) / LZ_PP_TILE);
+    c.timer.begin("k_settle_mismatch", c.stream);
+    if (!c.settle_mismatch_attr_set) { LZ_HIP(hipFuncSetAttribute((const void*)k_settle_mismatch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(LzSettle2Shared))); c.settle_mismatch_attr_set = true; }
+    hipLaunchKernelGGL(k_settle_mismatch, dim3(LZ_NBIN), dim3(LZ_S2_TPB), sizeof(LzSettle2Shared), c.stream, P, c.keys.as<u64>(), n_pp_tiles,
                        c.hist.as<u32>(), c.hist_part.as<u32>(), c.run_addr.as<u32>(), c.bin_base.as<u32>(),
                        c.diag_end.as<u32>(), c.hsp_out.as<LzHspRec>(), c.hsp_count.as<u32>(), out_cap);
     c.timer.end(c.stream);

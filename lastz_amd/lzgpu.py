@@ -76,7 +76,7 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
            "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_table_num_words",
            "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_table_limit", "lzgpu_table_find_limit", "lzgpu_table_count_distribution", "lzgpu_device_copy",
-           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_seed_hit_search_exact", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
+           "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_seed_hit_search_exact", "lzgpu_seed_hit_search_mismatch", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
            "lzgpu_set_bucket_owner", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
@@ -112,6 +112,7 @@ class Lib:
             self.L.lzgpu_seed_hit_search_self.argtypes = [C.POINTER(SearchArgs), C.POINTER(SelfArgs), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
             self.L.lzgpu_seed_hit_search_within.argtypes = [C.POINTER(SearchArgs), C.POINTER(PosFilter), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
             self.L.lzgpu_seed_hit_search_exact.argtypes = [C.POINTER(SearchArgs), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+            self.L.lzgpu_seed_hit_search_mismatch.argtypes = [C.POINTER(SearchArgs), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         f("table_prepare").argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                        C.POINTER(SeedDesc), C.c_uint32]
         f("set_hit_capacity").argtypes = [C.c_uint64]
@@ -280,6 +281,14 @@ class Lib:
     def seed_hit_search_exact(self, match_bits, length, q=None, slot=-1, start=0, end=0):
         """lastz --exact=<length>: the seed hits extended while bases match (match_bits = hp->charToBits, nuc_to_bits: lower
         case matches upper case, everything else matches nothing); HSPs of at least `length` bases, score == length"""
+        return self._search_matching(None, match_bits, length, q, slot, start, end)
+
+    def seed_hit_search_mismatch(self, match_bits, count, length, q=None, slot=-1, start=0, end=0):
+        """lastz --mismatch=<count>,<length>: the seed hits extended over at most `count` mismatches (match_bits as in
+        seed_hit_search_exact); HSPs of at least `length` bases, score == length"""
+        return self._search_matching(count, match_bits, length, q, slot, start, end)
+
+    def _search_matching(self, count, match_bits, length, q, slot, start, end):
         a = SearchArgs()
         mb = np.ascontiguousarray(match_bits, dtype=np.int8)
         assert len(mb) == 256
@@ -292,7 +301,10 @@ class Lib:
         a.sub, a.hsp_threshold = None, length
         out = C.c_void_p()
         n = C.c_uint64()
-        self._check(self.L.lzgpu_seed_hit_search_exact(C.byref(a), _ptr(mb), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search_exact")
+        if count is None:
+            self._check(self.L.lzgpu_seed_hit_search_exact(C.byref(a), _ptr(mb), C.byref(out), C.byref(n)), "lzgpu_seed_hit_search_exact")
+        else:
+            self._check(self.L.lzgpu_seed_hit_search_mismatch(C.byref(a), _ptr(mb), count, C.byref(out), C.byref(n)), "lzgpu_seed_hit_search_mismatch")
         res = np.zeros(n.value, dtype=HSP_DTYPE)
         if n.value:
             C.memmove(_ptr(res), out, n.value * HSP_DTYPE.itemsize)
