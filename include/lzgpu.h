@@ -273,6 +273,37 @@ int lzgpu_seed_hit_search_exact(const lz_search_args* args, const int8_t match_b
  * lzgpu_seed_hit_search_exact. */
 int lzgpu_seed_hit_search_mismatch(const lz_search_args* args, const int8_t match_bits[256], int32_t max_mismatches, lz_hsp** out, uint64_t* n_out);
 
+/* ---- B2 under a seed-hit filter (lastz --filter=[<T>,]<M>, --filter=cares:[<T>,]<M>) ----------------------------------
+ * filter_seed_hit_by_subs (src/seed_search.c:2346-2411), which process_for_simple_hit runs after the diagEnd test (:1113)
+ * and before any extension (:1056-1192), and process_for_plain_hit the same way (:995-1029): a seed hit is discarded unless
+ * its seed window holds at least min_matches matches and at most max_transversions transversions.  A sticky setting, like
+ * lzgpu_table_limit and lzgpu_set_bucket_owner: while set it applies to every later lzgpu_seed_hit_search, _self, _within,
+ * _exact and _mismatch, with extend 1 or 0; table calls do not lift it (lzgpu_shutdown does); lzgpu_window_search is not affected.
+ * Per counted position, with t and q the two bases: match_bits[t] < 0, match_bits[q] < 0 or a NUL byte counts as a
+ * transversion (:2374, :2392); equal bits count as a match (:2376, :2394); bits whose low bits differ count as a transversion
+ * (is_transversion, :2344, :2378, :2396); a transition counts as neither.  A hit is kept iff matches >= min_matches and
+ * (max_transversions < 0 or transversions <= max_transversions) (:2403-2410).
+ * A rejected hit writes nothing (it has only activated its bucket with diagEnd = 0, which the first surviving hit does as
+ * well), so the result is that of the same search over the raw hits with the failing ones taken out, order kept.
+ * A search under a filter returns LZGPU_ERR_ARG when positions is 0 or has a bit at or above the resident seed's length,
+ * when min_matches is negative or exceeds the number of counted positions (lastz chastises that, src/lastz.c:9797), or when
+ * it is an _exact / _mismatch search whose match_bits differ from the filter's (a slot caches one set of match codes); with
+ * bucket owners (lzgpu_set_bucket_owner) it returns LZGPU_NH_UNSUPPORTED before any work.
+ * Counters: words and raw_hits stay the unfiltered values (the reference counts raw hits at :865, before the processor);
+ * extensions, bp_extended and hsps are those of the surviving hits.  lzgpu_last_hsp_order keeps working.
+ * Costs 8 bytes (+ 1 bit) per hit of the largest chunk while set, the two-kernel path in the place of the fused one for an
+ * X-drop search, and one host synchronisation per chunk. */
+typedef struct lz_hit_filter {
+    int32_t  min_matches;        /* hp->minMatches, >= 0                                             */
+    int32_t  max_transversions;  /* hp->maxTransversions; < 0: no limit                              */
+    uint32_t positions;          /* bit k: base k of the seed window [pos - L, pos) counts (k = 0 the
+                                    leftmost, pattern[k]).  --filter=: the L low bits.  --filter=cares:
+                                    the bits with pattern[k] != '0' (hp->filterPattern)              */
+    int8_t   match_bits[256];    /* hp->charToBits                                                   */
+} lz_hit_filter;
+int lzgpu_set_hit_filter(const lz_hit_filter* f);     /* NULL lifts it */
+int lzgpu_last_filter_dropped(uint64_t* dropped);     /* raw hits the LAST search's filter removed */
+
 /* ---- B1 + B2 for many small rectangles of the two sequences at once ----------------------------
  * What src/tweener.c:769-829 (bounded_align) does for every in-between window of `lastz --inner=<score>`:
  * build_seed_position_table on target[t_off, t_off + t_len) with the inner seed, seed_hit_search of

@@ -553,7 +553,7 @@ u64 seed_hit_search
 	lz_hsp*        h = NULL;
 	uint64_t       n = 0, k;
 	u64            basesHit = 0;
-	int            rc, mismatchExtend;
+	int            rc, mismatchExtend, filtered = false;
 	char*          mmEnv;
 
 	if (twMode == twRecord)                                     /* a window of the tweener: noted, searched later with all the others */
@@ -598,7 +598,7 @@ u64 seed_hit_search
 	if ((pt != devTable) || (devTable == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
 	 || (processor != process_for_simple_hit) || ((hp->gfExtend != gfexXDrop) && (hp->gfExtend != gfexExact) && (!mismatchExtend))
 	 || (((hp->gfExtend == gfexExact) || (mismatchExtend)) && ((selfCompare) || (hp->posFilter) || (bandWidth != 0)))   /* --exact, --mismatch: alone, not with --self, --chores or --band */
-	 || (hp->hspThreshold.t != 'S') || ((hp->posFilter) && (selfCompare)) || (hp->minMatches >= 0) || (hp->reportEntropy)
+	 || (hp->hspThreshold.t != 'S') || ((hp->posFilter) && (selfCompare)) || (hp->reportEntropy)
 	 || ((!selfCompare) && (bandWidth != 0)) || (searchLimit != 0)
 	 || (seq2->fileType == seq_type_qdna) || (hp->seq1 != seq1) || (hp->seq2 != seq2)
 	 || (memcmp (upperCharToBits, devCharToBits, 256) != 0)
@@ -613,6 +613,19 @@ u64 seed_hit_search
 	a.start = start;    a.end = end;
 	a.sub   = (const int32_t*) hp->scoring->sub;
 	a.xdrop = hp->xDrop;  a.hsp_threshold = hp->hspThreshold.s;  a.entropic = hp->entropicHsp;  a.extend = 1;
+
+	if (hp->minMatches >= 0)                                    /* --filter=[<T>,]<M>, --filter=cares:[<T>,]<M>: filter_seed_hit_by_subs (src/seed_search.c:2346-2411) on the device, */
+		{                                                       /* set for this search, whichever of the routines below runs it, and lifted after it on every exit */
+		lz_hit_filter hf;
+		u32           L = hitSeed->length, i;
+		memset (&hf, 0, sizeof(hf));
+		hf.min_matches = hp->minMatches;  hf.max_transversions = hp->maxTransversions;
+		if (hp->filterPattern == NULL) hf.positions = (L >= 32)? 0xFFFFFFFFu : ((1u << L) - 1);
+		else for (i=0 ; (i<L)&&(i<32) ; i++) if (hp->filterPattern[i] != '0') hf.positions |= 1u << i;
+		memcpy (hf.match_bits, hp->charToBits, 256);
+		if (lzgpu_set_hit_filter (&hf) != 0) suicidef ("lzgpu_set_hit_filter: %s", lzgpu_last_error());
+		filtered = true;
+		}
 
 	if (hp->gfExtend == gfexExact)                              /* --exact=<length>: match_extend_seed_hit (src/seed_search.c:3018-3254) on the device, under hp->charToBits */
 		{
@@ -667,6 +680,7 @@ u64 seed_hit_search
 		rc = lzgpu_seed_hit_search (&a, &h, &n);
 		if (rc < 0) suicidef ("lzgpu_seed_hit_search: %s", lzgpu_last_error());
 		}
+	if (filtered) lzgpu_set_hit_filter (NULL);
 	if (rc > 0)
 		{ note ("search", "declined, reference path");  host_table_needed (pt);
 		  return ref_seed_hit_search (seq1, pt, seq2, start, end, selfCompare, upperCharToBits, hitSeed,

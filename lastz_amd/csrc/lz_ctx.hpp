@@ -108,6 +108,8 @@ struct LzCtx {
     DevBuf keys;                          // hit keys of a chunk, discovery order; on the fused path of scan mode 0
                                           // the chunk's tagged records instead (k_scan_hits2), and bins / summ are not allocated.  The partition kernels
                                           // turn it in place into the chunk's records, every tile sorted by partition (lz_tile_runs.hpp): 8 bytes per hit
+    DevBuf keys2;                         // under a hit filter (lzgpu_set_hit_filter): the second key buffer the surviving keys are moved to; changes places with keys
+    DevBuf filter_keep, filter_counts, filter_bases;   // ... the keep words (one bit per hit), the survivors per block of k_filter_mark and their exclusive scan
     DevBuf bin_base;                      // the 257 partition offsets (ranks)
     DevBuf hist, hist_part, run_addr;     // [tile][partition]: records, then first rank inside the block of 256 tiles; the blocks' first ranks; where the run lies
     DevBuf summ, scan_tasks, scan_ntasks; // phase A: 4-byte summary per hit of the chunk; the scans that go on past their first window
@@ -142,6 +144,9 @@ struct LzCtx {
     // 7 launches, 0.73 s at 2048; 5 launches, 0.48 s at 8192 and beyond).  Default: 1/32 of the anchors, within [2048, 16384].
     u32 dp_window = 0;                // 0: the default rule; lzgpu_set_dp_window fixes it (LZGPU_DP_WINDOW, for one call, goes before either)
     u32 n_owners = 1, owner = 0;      // bucket ownership (lzgpu_set_bucket_owner)
+    bool filter_on = false;           // a hit filter is in force (lzgpu_set_hit_filter); table calls do not lift it, lzgpu_shutdown does (as it resets n_owners)
+    lz_hit_filter filter = {};
+    u64 filter_dropped = 0;           // raw hits the last search's filter removed (lzgpu_last_filter_dropped)
     LzSelfDev self = {};              // the self-comparison filter of the search in progress (lzgpu_seed_hit_search_self) or its position filter (lzgpu_seed_hit_search_within); mode LZ_SELF_OFF otherwise
     DevBuf self_sep;                  // its separators on the device: sep1, then sep2
     std::vector<u64> last_order;      // two sort words per HSP of the last search
@@ -159,7 +164,7 @@ struct LzCtx {
     // describes their contents -- nothing outlives the device context it was made on
     void release_device_memory()
     {
-        DevBuf* all[] = { &wstart, &wpos, &full_wstart, &full_wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &bin_base, &hist, &hist_part, &run_addr,
+        DevBuf* all[] = { &wstart, &wpos, &full_wstart, &full_wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &keys2, &filter_keep, &filter_counts, &filter_bases, &bin_base, &hist, &hist_part, &run_addr,
                           &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab, &match_tmp,
                           &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep,
                           &dp.jobs, &dp.ids, &dp.res, &dp.tab, &dp.tb, &dp.rows, &dp.ops, &dp.ops_off, &dp.ops_out, &dp.pieces, &dp.rings, &dp.sel_jobs, &dp.sel_res, &dp.problems,
@@ -184,7 +189,7 @@ int lz_fail(int code, const char* fmt, ...);
 
 // ---- the seed stage's launchers: all asynchronous on c.stream (lzk_encode: or the stream it is given).  A launcher is passed what
 // varies per call -- the chunk, the kernels' parameters, the mode -- and reads the buffers that are members of LzCtx from c. ----
-struct LzChunk; struct LzLutParams; struct LzExactParams; struct LzMismatchParams;     // lz_host.hpp, lz_lut.hpp, lz_exact.hpp
+struct LzChunk; struct LzLutParams; struct LzExactParams; struct LzMismatchParams; struct LzFilterParams;     // lz_host.hpp, lz_lut.hpp, lz_exact.hpp, lz_filter.hpp
 #include "lz_tile_runs.hpp"         // LZ_PP_TILE_HOST: hits per tile of k_partition (sizes the tile tables)
 // seq_kernels.hip
 int lzk_encode(LzCtx& c, const u8* raw, u8* code, u32 len, const u8* cls256_dev, hipStream_t st = nullptr, KernelTimer* timer = nullptr);   // defaults: c.stream, c.timer
@@ -221,3 +226,6 @@ int lzk_settle_mismatch(LzCtx& c, const LzMismatchParams& P, u64 n, u32 out_cap)
 int lzk_scan_exact(LzCtx& c, const LzExactParams& P, u64 n);             // phase A of an exact-match search: c.keys -> c.summ (sized by the caller)
 // mismatch_kernels.hip
 int lzk_scan_mismatch(LzCtx& c, const LzMismatchParams& P, u64 n);       // phase A of an N-mismatch search, likewise
+// filter_kernels.hip
+int lzk_filter_reserve(LzCtx& c, u64 max_n);                             // c.keys2 and the filter's scratch for chunks of up to max_n hits
+int lzk_filter_hits(LzCtx& c, const LzFilterParams& F, u64 n, u64* n_kept);   // c.keys -> the keys the hit filter keeps, in order (c.keys and c.keys2 change places); synchronises c.stream

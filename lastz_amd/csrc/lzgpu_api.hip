@@ -18,6 +18,7 @@
 #include "lz_lut.hpp"
 #include "lz_exact.hpp"
 #include "lz_mismatch.hpp"
+#include "lz_filter.hpp"
 
 // ------------------------------------------------------------------------------ context
 
@@ -213,6 +214,7 @@ extern "C" void lzgpu_shutdown(void)
     if (c.dp_stream) (void)hipStreamDestroy(c.dp_stream);
     c.stream = nullptr; c.dp_stream = nullptr; c.inited = false; c.device = -1;
     c.n_owners = 1; c.owner = 0; c.last_order.clear();
+    c.filter_on = false; c.filter_dropped = 0;
 }
 
 extern "C" void lzgpu_free(void* p) { free(p); }
@@ -631,7 +633,7 @@ static int search_enter(bool args_ok, lz_hsp** out, uint64_t* n_out)
 {
     int rc = require_init(); if (rc) return rc;
     if (!args_ok) return lz_fail(LZGPU_ERR_ARG, "null argument");
-    *out = nullptr; *n_out = 0;
+    *out = nullptr; *n_out = 0; g_ctx.filter_dropped = 0;
     if (!g_ctx.have_table) return lz_fail(LZGPU_ERR_STATE, "lzgpu_table_prepare has not been called");
     return 0;
 }
@@ -648,6 +650,7 @@ struct SeedSearch {                                             // a seed_search
     bool exact() const { return match_bits != nullptr; }
     bool extend() const { return exact() || a->extend != 0; }
     LzExtendParams P; LzLutParams Q; LzExactParams X; LzMismatchParams MM;
+    bool filtered = false; LzFilterParams F;                    // a hit filter is in force (lzgpu_set_hit_filter): every chunk's keys pass lzk_filter_hits
     u32 out_cap = 0;
     std::vector<lz_hsp> plain;                                  // !a->extend: every hit
 };
@@ -700,6 +703,10 @@ static int ss_classes(LzCtx& c, SeedSearch& s)
     if ((rc = slot_encode(c, c.target, cls, c.cls_t))) return rc;
     lzh_make_cls(c.colc, c.geom.char_to_bits, cls);
     if ((rc = slot_encode(c, *s.qs, cls, c.cls_q))) return rc;
+    if (s.filtered) {                                           // the match codes the filter reads, beside the scoring codes (one encode pass each, cached by match_bits)
+        if ((rc = slot_match_encode(c, c.target, c.filter.match_bits))) return rc;
+        if ((rc = slot_match_encode(c, *s.qs, c.filter.match_bits))) return rc;
+    }
     g_hp.lap(0, "upload+classes+encode");
     return 0;
 }
@@ -773,6 +780,12 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
 {
     const lz_search_args* a = s.a;
     SeqSlot* qs = s.qs;
+    if (s.filtered) {
+        LzFilterParams& F = s.F;
+        F.t2 = c.target.mtwo.as<u8>(); F.tsp = c.target.mspc.as<u8>(); F.q2 = qs->mtwo.as<u8>(); F.qsp = qs->mspc.as<u8>();
+        F.pos_spread = lz_filter_spread(c.filter.positions); F.seed_len = s.L;
+        F.min_matches = c.filter.min_matches; F.max_transversions = c.filter.max_transversions;
+    }
     if (s.exact()) {                                            // k_scan_exact: no mode, no tables, never fused
         LzExactParams& X = s.X;
         X.t2 = c.target.mtwo.as<u8>(); X.tsp = c.target.mspc.as<u8>(); X.q2 = qs->mtwo.as<u8>(); X.qsp = qs->mspc.as<u8>();
@@ -811,9 +824,9 @@ static int ss_scan_mode(LzCtx& c, SeedSearch& s)
     s.mode = c.last_scan_mode = mode;
     // scan mode 0 takes the fused path (k_scan_hits2: enumeration + phase A over the context-inlined table, tagged
     // records in keys and neither summaries nor partition bytes) unless LZGPU_FUSED_SCAN=0 asks for the two kernels,
-    // the fill variant in use is one the fused kernel does not reproduce (bucket owners), or
-    // wctx cannot be had (lz_wctx_prepare)
-    s.fused = a->extend && mode == 0 && s.max_chunk && lz_settings().fused_scan && c.n_owners <= 1;
+    // the fill variant in use is one the fused kernel does not reproduce (bucket owners), a hit filter needs the key stream
+    // between the two kernels (lzk_filter_hits), or wctx cannot be had (lz_wctx_prepare)
+    s.fused = a->extend && mode == 0 && s.max_chunk && lz_settings().fused_scan && c.n_owners <= 1 && !s.filtered;
     if (s.fused && (rc = lz_wctx_prepare(c, s.fused))) return rc;
     return 0;
 }
@@ -827,6 +840,7 @@ static int ss_reserve(LzCtx& c, SeedSearch& s)
     if (max_chunk) {
         if ((rc = c.keys.ensure((size_t)max_chunk * 8))) return rc;
         if (!s.fused && (rc = c.bins.ensure((size_t)max_chunk + 64))) return rc;       // k_fill_hits writes a partition byte per hit on every path (the plain-hit path included)
+        if (s.filtered && (rc = lzk_filter_reserve(c, max_chunk))) return rc;          // (only while a filter is in force: 8 bytes per hit more)
     }
     if (extend && max_chunk) {
         const size_t ntiles = (size_t)((max_chunk + LZ_PP_TILE_HOST - 1) / LZ_PP_TILE_HOST), nblocks = (ntiles + 255) / 256;
@@ -844,36 +858,53 @@ static int ss_reserve(LzCtx& c, SeedSearch& s)
 
 // ---- 7. one chunk: enumeration + phase A (one launch or two), the records sorted tile by tile where they lie, the runs'
 // ranks from the counts that leaves, phase B.  All on c.stream: diagEnd carries from chunk to chunk, in chunk order.
+// (under a hit filter, after the fill: the chunk's keys compacted to those the filter keeps, nh their number from here on)
+static int ss_filter(LzCtx& c, SeedSearch& s, u64& nh)
+{
+    if (!s.filtered) return 0;
+    u64 kept = 0;
+    int rc = lzk_filter_hits(c, s.F, nh, &kept); if (rc) return rc;
+    c.filter_dropped += nh - kept;
+    nh = kept;
+    return 0;
+}
 static int ss_chunk(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
-    int rc;
+    int rc; u64 nh = ch.nh;
     if (s.fused) {
         if ((rc = lzk_scan_fused(c, s.lo, ch, s.n, s.P, s.Q))) return rc;
     } else {
         if ((rc = lzk_fill_hits(c, s.lo, ch, s.n))) return rc;
-        if ((rc = lzk_scan_hits(c, s.mode, s.P, s.Q, ch.nh))) return rc;
+        if ((rc = ss_filter(c, s, nh))) return rc;
+        if (nh == 0) return 0;                                  // (a chunk without a survivor launches nothing more; diagEnd carries over untouched)
+        if ((rc = lzk_scan_hits(c, s.mode, s.P, s.Q, nh))) return rc;
     }
-    if ((rc = lzk_partition(c, s.fused, ch.nh))) return rc;
-    if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
-    return lzk_settle(c, s.P, ch.nh, s.out_cap);
+    if ((rc = lzk_partition(c, s.fused, nh))) return rc;
+    if ((rc = lzk_hist_scan(c, nh))) return rc;
+    return lzk_settle(c, s.P, nh, s.out_cap);
 }
 // ... of an exact-match search: k_scan_exact and k_settle_exact in the places of the X-drop kernels, everything between them as it is;
 // of an N-mismatch search: k_scan_mismatch and k_settle_mismatch there
 static int ss_chunk_exact(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
-    int rc;
+    int rc; u64 nh = ch.nh;
     if ((rc = lzk_fill_hits(c, s.lo, ch, s.n))) return rc;
-    if ((rc = s.mismatches ? lzk_scan_mismatch(c, s.MM, ch.nh) : lzk_scan_exact(c, s.X, ch.nh))) return rc;
-    if ((rc = lzk_partition(c, false, ch.nh))) return rc;
-    if ((rc = lzk_hist_scan(c, ch.nh))) return rc;
-    return s.mismatches ? lzk_settle_mismatch(c, s.MM, ch.nh, s.out_cap) : lzk_settle_exact(c, s.X, ch.nh, s.out_cap);
+    if ((rc = ss_filter(c, s, nh))) return rc;
+    if (nh == 0) return 0;
+    if ((rc = s.mismatches ? lzk_scan_mismatch(c, s.MM, nh) : lzk_scan_exact(c, s.X, nh))) return rc;
+    if ((rc = lzk_partition(c, false, nh))) return rc;
+    if ((rc = lzk_hist_scan(c, nh))) return rc;
+    return s.mismatches ? lzk_settle_mismatch(c, s.MM, nh, s.out_cap) : lzk_settle_exact(c, s.X, nh, s.out_cap);
 }
 // ... of a search without extension (process_for_plain_hit): every hit is reported
 static int ss_chunk_plain(LzCtx& c, SeedSearch& s, const LzChunk& ch)
 {
     int rc = lzk_fill_hits(c, s.lo, ch, s.n); if (rc) return rc;
-    std::vector<u64> hk(ch.nh);
-    LZ_HIP(hipMemcpyAsync(hk.data(), c.keys.p, (size_t)ch.nh * 8, hipMemcpyDeviceToHost, c.stream));
+    u64 nh = ch.nh;
+    if ((rc = ss_filter(c, s, nh))) return rc;
+    if (nh == 0) return 0;
+    std::vector<u64> hk(nh);
+    LZ_HIP(hipMemcpyAsync(hk.data(), c.keys.p, (size_t)nh * 8, hipMemcpyDeviceToHost, c.stream));
     LZ_HIP(hipStreamSynchronize(c.stream));
     for (u64 k : hk) { u32 p2 = (u32)k; s.plain.push_back({ p2 + (u32)(k >> 32), p2, s.L, 0 }); }
     return 0;
@@ -923,6 +954,21 @@ static int ss_finish(LzCtx& c, SeedSearch& s, lz_hsp** out, uint64_t* n_out)
     return 0;
 }
 
+// The hit filter in force against the resident seed and this search, before any work (include/lzgpu.h, lzgpu_set_hit_filter)
+static int filter_check(LzCtx& c, const int8_t* match_bits)
+{
+    if (!c.filter_on) return 0;
+    const lz_hit_filter& f = c.filter;
+    const u32 L = (u32)c.seed.length;
+    if (f.positions == 0 || (L < 32 && (f.positions >> L) != 0)) return lz_fail(LZGPU_ERR_ARG, "hit filter: positions %08x of a seed of length %u", f.positions, L);
+    if (f.min_matches < 0 || f.min_matches > __builtin_popcount(f.positions))
+        return lz_fail(LZGPU_ERR_ARG, "hit filter: %d matches of %d positions", (int)f.min_matches, __builtin_popcount(f.positions));    // src/lastz.c:9797
+    if (match_bits && memcmp(match_bits, f.match_bits, 256) != 0)
+        return lz_fail(LZGPU_ERR_ARG, "hit filter: the search's match_bits differ from the filter's (a slot holds one set of match codes)");
+    if (c.n_owners > 1) return LZGPU_NH_UNSUPPORTED;             // (the owner path is not tested with the filter kernels)
+    return 0;
+}
+
 // the search proper (after search_enter); with c.self.mode != LZ_SELF_OFF the count, fill and fused scan kernels drop
 // the hits a self-comparison drops
 static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out, const int8_t* match_bits = nullptr, u32 mismatches = 0)
@@ -930,6 +976,9 @@ static int seed_search(const lz_search_args* a, lz_hsp** out, uint64_t* n_out, c
     LzCtx& c = g_ctx;
     SeedSearch s; s.a = a; s.match_bits = match_bits; s.mismatches = mismatches;
     int rc;
+    c.filter_dropped = 0;
+    if ((rc = filter_check(c, match_bits))) return rc;
+    s.filtered = c.filter_on;
     g_hp.start();
     if ((rc = ss_query(c, s))) return rc;
     if ((rc = ss_classes(c, s))) return rc;
@@ -1113,6 +1162,18 @@ extern "C" int lzgpu_set_bucket_owner(uint32_t n_owners, uint32_t owner)
 {
     if (n_owners < 1 || n_owners > LZ_DIAG_SIZE || owner >= n_owners) return LZGPU_ERR_ARG;
     g_ctx.n_owners = n_owners; g_ctx.owner = owner;
+    return 0;
+}
+extern "C" int lzgpu_set_hit_filter(const lz_hit_filter* f)
+{
+    g_ctx.filter_on = f != nullptr;
+    if (f) g_ctx.filter = *f;
+    return 0;
+}
+extern "C" int lzgpu_last_filter_dropped(uint64_t* dropped)
+{
+    if (!dropped) return LZGPU_ERR_ARG;
+    *dropped = g_ctx.filter_dropped;
     return 0;
 }
 extern "C" int lzgpu_last_hsp_order(uint64_t* out, uint64_t n)

@@ -60,6 +60,10 @@ class PosFilter(C.Structure):
     _fields_ = [("t_start", C.c_uint32), ("t_end", C.c_uint32), ("q_start", C.c_uint32), ("q_end", C.c_uint32)]
 
 
+class HitFilter(C.Structure):
+    _fields_ = [("min_matches", C.c_int32), ("max_transversions", C.c_int32), ("positions", C.c_uint32), ("match_bits", C.c_int8 * 256)]
+
+
 class Counters(C.Structure):
     _fields_ = [("words", C.c_uint64), ("raw_hits", C.c_uint64), ("extensions", C.c_uint64),
                 ("bp_extended", C.c_uint64), ("hsps", C.c_uint64), ("dp_cells", C.c_uint64),
@@ -79,7 +83,7 @@ EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device
            "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_seed_hit_search_exact", "lzgpu_seed_hit_search_mismatch", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
            "lzgpu_profile_get", "lzgpu_set_hit_capacity", "lzgpu_set_hsp_capacity", "lzgpu_set_dp_slot", "lzgpu_set_dp_window", "lzgpu_dp_longest",
-           "lzgpu_set_bucket_owner", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
+           "lzgpu_set_bucket_owner", "lzgpu_set_hit_filter", "lzgpu_last_filter_dropped", "lzgpu_last_hsp_order", "lzgpu_last_scan_mode", "lzgpu_set_scan_mode", "lzgpu_reduce_to_chain", "lzgpu_reduce_to_chain_batch"]
 
 
 class LzGpuError(RuntimeError):
@@ -340,6 +344,29 @@ class Lib:
 
     def set_bucket_owner(self, n_owners, owner):
         self._check(self._f("set_bucket_owner")(C.c_uint32(n_owners), C.c_uint32(owner)), "lzgpu_set_bucket_owner")
+
+    def set_hit_filter(self, match_bits=None, min_matches=0, max_transversions=-1, positions=0):
+        """lastz --filter=[<T>,]<M>: from now on every seed search drops the raw hits whose window has fewer than min_matches
+        matches or more than max_transversions transversions (< 0: no limit) among the bases of `positions` (bit k: base k
+        of the window, the leftmost first; --filter=cares: the seed's non-0 positions).  match_bits = hp->charToBits.
+        None lifts the filter."""
+        self.L.lzgpu_set_hit_filter.argtypes = [C.c_void_p]
+        if match_bits is None:
+            self._check(self.L.lzgpu_set_hit_filter(None), "lzgpu_set_hit_filter")
+            return
+        f = HitFilter()
+        f.min_matches, f.max_transversions, f.positions = min_matches, max_transversions, positions
+        mb = np.ascontiguousarray(match_bits, dtype=np.int8)
+        assert len(mb) == 256
+        C.memmove(f.match_bits, _ptr(mb), 256)
+        self._check(self.L.lzgpu_set_hit_filter(C.byref(f)), "lzgpu_set_hit_filter")
+
+    def last_filter_dropped(self):
+        """raw hits the hit filter removed from the last search"""
+        n = C.c_uint64()
+        self.L.lzgpu_last_filter_dropped.argtypes = [C.POINTER(C.c_uint64)]
+        self._check(self.L.lzgpu_last_filter_dropped(C.byref(n)), "lzgpu_last_filter_dropped")
+        return int(n.value)
 
     def table_save(self, path):
         self._check(self.L.lzgpu_table_save(str(path).encode()), "lzgpu_table_save")
