@@ -18,6 +18,12 @@
         }
     };
     auto block_end = [&]() -> u32 { return (u32)__builtin_amdgcn_readlane((int)bf[LZ_TR_K - 1], 63); };
+    auto entry_of = [&](const u32* b, u32 e) -> u32 {           // bf / ba of block entry e (wave-uniform)
+        u32 v = (u32)__builtin_amdgcn_readlane((int)b[0], (int)(e / LZ_TR_K));
+#pragma unroll
+        for (int j = 1; j < LZ_TR_K; j++) { const u32 vj = (u32)__builtin_amdgcn_readlane((int)b[j], (int)(e / LZ_TR_K)); if (e % LZ_TR_K == (u32)j) v = vj; }
+        return v;
+    };
     auto window_first = [&](u32 tt) -> u32 { return r0 + tt * (u32)LZ_S2_TILE + sw * (64u * LZ_S2_ROUNDS); };
     // one step of the cursor ahead of load_tile(tt), where the loads have a whole placement to arrive (the usual tile
     // needs no more than this one: 5376 ranks are about 84 partition tiles)
@@ -30,54 +36,58 @@
         const u32 g0 = window_first(tt);
         if (tt >= ntiles || g0 >= r1) return;                   // (wave-uniform)
         const u32 g1 = (r1 - g0 < 64u * LZ_S2_ROUNDS) ? r1 : g0 + 64u * LZ_S2_ROUNDS;
-        u8* const own = sh.own[sw];
         u32 idx[LZ_S2_ROUNDS] = {};
         for (;;) {
             const u32 bend = block_end();
             if (!lz_tr_block_behind(bend, g0)) {
-                // the runs of the block that hold ranks of the window mark their first one with 1 + their entry; a
-                // running maximum over the window then names every rank's run (k_fill_hits2's own[])
-                if (lane < 64u * LZ_S2_ROUNDS / 8u) reinterpret_cast<u64*>(own)[lane] = 0ull;
-                u32 dl[LZ_TR_K];
-#pragma unroll
-                for (int j = 0; j < LZ_TR_K; j++) {
-                    const u32 nf = j + 1 < LZ_TR_K ? bf[(j + 1) % LZ_TR_K] : (u32)__shfl_down((int)bf[0], 1);    // the next tile's first rank
-                    u32 pos;
-                    const bool m = lz_tr_mark(bf[j], nf, g0, g1, pos) && !(j == LZ_TR_K - 1 && lane == 63u);   // (the last entry only bounds the block)
-                    if (m) own[pos] = (u8)(1u + lane * LZ_TR_K + (u32)j);
-                    dl[j] = lz_tr_delta(ba[j], bf[j]);
-                }
+                // the block covers the ranks [s, lim) of the window.  Its entries ascend, so the run that holds s is a count
+                // away; from there one wave-uniform cursor (entry e, its displacement, the next entry's first rank) goes
+                // through the rounds, and a round's lanes at or beyond a run's first rank take that run's displacement
+                // (lz_tile_runs.hpp: the entry cursor).  A round meets about one run boundary.
                 const u32 bfirst = (u32)__builtin_amdgcn_readlane((int)bf[0], 0);
-                u32 carry = 0;
+                const u32 s = lz_tc_start(g0, bfirst), lim = lz_tc_limit(g1, bend);
+                if (s < lim) {                                  // (not so: the block's runs are all empty)
+                    u32 e = ~0u;
 #pragma unroll
-                for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
-                    const u32 g = g0 + (u32)rr * 64u + lane;
-                    const u32 mk = own[(u32)rr * 64u + lane];
-                    u32 v = mk;
-                    LZ_WAVE_SCAN_U32(v, mk, lz_umax)
-                    v = lz_umax(v, carry);
-                    carry = (u32)__builtin_amdgcn_readlane((int)v, 63);
-                    const u32 e = v - 1u;                       // (v == 0: a rank below the block, not covered)
-                    u32 d = (u32)__shfl((int)dl[0], (int)(e / LZ_TR_K));
+                    for (int j = 0; j < LZ_TR_K; j++) e += (u32)__popcll(__ballot(lz_tc_at_or_below(bf[j], s)));
+                    u32 nf = entry_of(bf, e + 1u);              // (e + 1 <= LZ_TR_BLOCK - 1: the bounding entry lies above s)
+                    u32 dcur = lz_tr_delta(entry_of(ba, e), entry_of(bf, e));
 #pragma unroll
-                    for (int j = 1; j < LZ_TR_K; j++) { const u32 dj = (u32)__shfl((int)dl[j], (int)(e / LZ_TR_K)); if (e % LZ_TR_K == (u32)j) d = dj; }
-                    if (lz_tr_covers(g, bfirst, bend, g1)) idx[rr] = lz_tr_index(g, d);
+                    for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
+                        const u32 base = g0 + (u32)rr * 64u, g = base + lane;
+                        u32 d = dcur;
+                        while (lz_tc_step(nf, base, lim)) {     // (stops below the bounding entry: its first rank is bend >= lim)
+                            e++;
+                            dcur = lz_tr_delta(entry_of(ba, e), nf);
+                            if (lz_tc_take(g, nf)) d = dcur;
+                            nf = entry_of(bf, e + 1u);
+                        }
+                        if (lz_tr_covers(g, bfirst, bend, g1)) idx[rr] = lz_tr_index(g, d);
+                    }
                 }
                 if (bend >= g1) break;
             }
             cur += LZ_TR_BLOCK - 1; load_block();               // (a sparse partition: the window goes on in later tiles)
         }
+        if (g1 - g0 == 64u * LZ_S2_ROUNDS) {                    // a full window (wave-uniform): every tile but a partition's last
 #pragma unroll
-        for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
-            if (g0 + (u32)rr * 64u + lane < g1) x[rr] = LZ_NT_LD(recs + (size_t)idx[rr]);
+            for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) x[rr] = LZ_NT_LD(recs + (size_t)idx[rr]);
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
+                if (g0 + (u32)rr * 64u + lane < g1) x[rr] = LZ_NT_LD(recs + (size_t)idx[rr]);
+        }
     };
-    auto count_tile = [&](u32 tt, const u64* x, u32* slot) {    // ranks inside (wave, bucket) -> slot[], totals -> cnt[tt & 1][sw][]
+    // count_tile / place_tile with full = true (a literal at the call: a copy without the per-round `valid` branches): every
+    // lane holds a record in every round, as in all windows of all tiles but a partition's last
+    auto full_window = [&](u32 tt) -> bool { return tt < ntiles && window_first(tt) < r1 && r1 - window_first(tt) >= 64u * LZ_S2_ROUNDS; };
+    auto count_tile = [&](u32 tt, const u64* x, u32* slot, const bool full) {    // ranks inside (wave, bucket) -> slot[], totals -> cnt[tt & 1][sw][]
         u32* const row = sh.cnt[tt & 1u][sw];
         reinterpret_cast<uint4*>(row)[lane] = make_uint4(0u, 0u, 0u, 0u);
         u64* const bmr = sh.bm[sw];
 #pragma unroll
         for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) {
-            const bool valid = x[rr] != ~0ull;
+            const bool valid = full || x[rr] != ~0ull;
             const u32 b = LZ_REC_LOW8(x[rr]);
             if (valid) atomicOr((unsigned long long*)&bmr[b], 1ull << lane);
             const u64 peers = valid ? bmr[b] : 0ull;
@@ -87,7 +97,7 @@
             slot[rr] = old + rank;
         }
     };
-    auto place_tile = [&](u32 tt, const u64* x, const u32* slot) {
+    auto place_tile = [&](u32 tt, const u64* x, const u32* slot, const bool full) {
         // bucket bases of the tile: every sorter wave sums the 12 rows for its own use (lane l: buckets 4l .. 4l+3)
         const u32 (*cn)[LZ_NBIN] = sh.cnt[tt & 1u];
         uint4 tot = make_uint4(0u, 0u, 0u, 0u), pre = tot;
@@ -110,7 +120,7 @@
         u64* const dst = sh.rec[tt & 1u];
 #pragma unroll
         for (int rr = 0; rr < LZ_S2_ROUNDS; rr++)
-            if (x[rr] != ~0ull) dst[sh.woff[sw][LZ_REC_LOW8(x[rr])] + slot[rr]] = x[rr];
+            if (full || x[rr] != ~0ull) dst[sh.woff[sw][LZ_REC_LOW8(x[rr])] + slot[rr]] = x[rr];
     };
 
     // ---- the two roles run their own loops (the register allocator sees two disjoint sets of live values) and
@@ -119,22 +129,22 @@
     if (!walker) {
         // prologue: tile 0 counted | tile 0 placed, tile 1 counted | then per interval t: tile t+1 placed, tile t+2 counted
         load_block();
-        load_tile(0, cx); load_tile(1, nx); count_tile(0, cx, cslot);
+        load_tile(0, cx); load_tile(1, nx); count_tile(0, cx, cslot, false);
         __syncthreads();
-        place_tile(0, cx, cslot);
+        place_tile(0, cx, cslot, false);
 #pragma unroll
         for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) cx[rr] = nx[rr];
         load_tile(2, nx);
-        count_tile(1, cx, cslot);
+        count_tile(1, cx, cslot, false);
         __syncthreads();
         for (u32 t = 0; t < ntiles; t++) {
             LZ_S2_CLK_BEGIN(sw == 0 && lane == 0);
             advance_early(t + 3);
-            if (t + 1 < ntiles) place_tile(t + 1, cx, cslot);
+            if (full_window(t + 1)) place_tile(t + 1, cx, cslot, true); else if (t + 1 < ntiles) place_tile(t + 1, cx, cslot, false);
 #pragma unroll
             for (int rr = 0; rr < LZ_S2_ROUNDS; rr++) cx[rr] = nx[rr];
             load_tile(t + 3, nx);                               // (past the last tile: no loads, "no record")
-            if (t + 2 < ntiles) count_tile(t + 2, cx, cslot);
+            if (full_window(t + 2)) count_tile(t + 2, cx, cslot, true); else if (t + 2 < ntiles) count_tile(t + 2, cx, cslot, false);
             LZ_S2_CLK_MID(sw == 0 && lane == 0, 2);
             __syncthreads();
             LZ_S2_CLK_END(sw == 0 && lane == 0, 3);

@@ -11,7 +11,9 @@
 // k_settle2's sorter waves gather 64 x LZ_S2_ROUNDS consecutive ranks at a time (a "window") through a cursor that only
 // moves forward: a block of LZ_TR_BLOCK consecutive tiles' (first, run_addr), LZ_TR_K per lane, whose last entry only
 // bounds the block (ranks below its `first` are covered).  The functions here are that arithmetic, per entry and per
-// rank (LZ_HD: also compiled for the host by tests/emul/emul_tile_runs.cpp, which replays the wave's procedure).
+// rank (LZ_HD: also compiled for the host by tests/emul/emul_tile_runs.cpp and emul_tile_cursor.cpp, which replay the
+// wave's procedure: the first with a mark per run and a running maximum over the window, as k_settle2 did it until the
+// entry cursor below, the second with that cursor).
 #pragma once
 #include "lz_common.hpp"
 
@@ -43,3 +45,17 @@ LZ_HD u32 lz_tr_index(u32 g, u32 delta) { return g + delta; }
 // a block whose bounding entry has first == block_end covers the ranks [block_first, block_end)
 LZ_HD bool lz_tr_block_behind(u32 block_end, u32 g0) { return block_end <= g0; }          // nothing of [g0, ..) in it: move on
 LZ_HD bool lz_tr_covers(u32 g, u32 block_first, u32 block_end, u32 g1) { return g >= block_first && g < block_end && g < g1; }
+
+// ---- the entry cursor: inside a block that is not behind the window [g0, g1), the ranks it covers are [s, lim) with
+//   s = lz_tc_start(g0, block_first), lim = lz_tc_limit(g1, block_end)          (nothing if s >= lim: a block of empty runs)
+// The entries' `first` ascend, so the run that holds s is entry (block entries with lz_tc_at_or_below(first, s)) - 1: of
+// equal ones (empty runs) the last, and never the bounding entry, whose first = block_end > s.  From there the wave goes
+// through the window in rounds of 64 ranks with one wave-uniform cursor (entry e, its displacement, first of entry e + 1):
+// while lz_tc_step(next_first, round_base, lim) it moves to entry e + 1, whose displacement the lanes with
+// lz_tc_take(rank, next_first) take over; the cursor carries from round to round.  first(bounding entry) = block_end >= lim
+// ends it, so the bounding entry is never taken as a run.  An empty run costs one trip.
+LZ_HD u32 lz_tc_start(u32 g0, u32 block_first) { return block_first > g0 ? block_first : g0; }
+LZ_HD u32 lz_tc_limit(u32 g1, u32 block_end) { return block_end < g1 ? block_end : g1; }
+LZ_HD bool lz_tc_at_or_below(u32 first, u32 s) { return first <= s; }
+LZ_HD bool lz_tc_step(u32 next_first, u32 round_base, u32 lim) { return next_first < lim && next_first < round_base + 64u; }
+LZ_HD bool lz_tc_take(u32 g, u32 next_first) { return g >= next_first; }

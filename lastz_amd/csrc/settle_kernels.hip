@@ -311,10 +311,8 @@ struct LzSettle2Shared {
     u32 cnt[2][LZ_S2_SORTW][LZ_NBIN];                    // records per (wave, bucket) of the tile being counted / placed
     u32 woff[LZ_S2_SORTW][LZ_NBIN];                      // where wave w's records of bucket b start in the placed tile
     u32 lbeg[2][LZ_NBIN], lcnt[2][LZ_NBIN];              // bucket lists of the placed tiles
-    alignas(8) u8 own[LZ_S2_SORTW][64 * LZ_S2_ROUNDS];   // load_tile: per rank of a wave's window, 1 + the block entry of the run that starts there
 };
 static_assert(sizeof(LzSettle2Shared) <= 160 * 1024, "k_settle2: one workgroup per CU");
-static_assert(LZ_TR_BLOCK <= 255 && (64 * LZ_S2_ROUNDS) % 8 == 0, "own[] holds 1 + a block entry per byte, cleared 8 at a time");
 __global__ void __launch_bounds__(LZ_S2_TPB)
 k_settle2(LzExtendParams P, const u64* __restrict__ recs, u32 n_pp_tiles, const u32* __restrict__ hist, const u32* __restrict__ hist_part,
           const u32* __restrict__ run_addr, const u32* __restrict__ bin_base, u32* __restrict__ diag_end,
