@@ -110,6 +110,26 @@ int lzgpu_table_export(uint32_t* last, uint32_t* prev);
  * fences lie outside the interval its position filter admits).  The target's encodings are redone by the next search or
  * gapped call, a pass over the target each.  LZGPU_ERR_ARG for a position past the end (nothing is written then). */
 int lzgpu_target_patch(const uint32_t* pos, const uint8_t* bytes, uint32_t n);
+/* The range form of lzgpu_target_patch: t[start + k] = bytes[k], k < len, in one copy, on the device and in the
+ * library's host copy (the bases lastz --masking turns into 'x').  The position table is left as it is (see
+ * lzgpu_table_mask); the target's encodings are redone by the next call that needs them.  LZGPU_ERR_ARG when the range
+ * reaches past the end of the target (nothing is written then). */
+int lzgpu_target_update(uint32_t start, const uint8_t* bytes, uint32_t len);
+/* Dynamic masking (lastz --masking=<count>): mask_seed_position_table (src/pos_table.c:747-887) for n intervals at once.
+ * An interval is origin 0, end-exclusive, already widened as src/lastz.c:3797-3801 widens it.  Every entry p (a word's END
+ * position) of the resident table with iv[k].start + L <= p <= iv[k].end for some k, L the seed length, leaves the
+ * table; everything else keeps its place in its list.  The decision reads no byte of the target.  Intervals may overlap,
+ * repeat, be shorter than L (they then remove nothing, :835) and reach beyond the table's [start, end).
+ * end <= start or end > tlen: LZGPU_ERR_ARG, nothing changes (the reference stops on those).  n == 0, or a call that
+ * removes nothing, leaves the table as it is.  Afterwards lzgpu_table_num_words, _geom, _export, _buffers, _save,
+ * _count_distribution, _find_limit and every search see the masked table.  While a word-count limit is in force
+ * (lzgpu_table_limit) or with bucket owners: LZGPU_NH_UNSUPPORTED, nothing changes.  LZGPU_ERR_STATE without a table.
+ * Costs one pass over the table's entries, and allocates nothing once its scratch has grown to the table's size.  The
+ * table is rewritten in place: a device error during the rewrite (LZGPU_ERR_HIP) leaves NO table -- later table calls
+ * return LZGPU_ERR_STATE until one is made again.  The ranges are merged on the host first, so no number or overlap of
+ * intervals is too much. */
+typedef struct lz_interval { uint32_t start, end; } lz_interval;
+int lzgpu_table_mask(const lz_interval* iv, uint32_t n);
 /* Rebuild the table from the target bytes already resident in HBM (same geometry as the last
  * lzgpu_table_prepare); used to time B1 without the host->device copy. */
 int lzgpu_table_rebuild(void);

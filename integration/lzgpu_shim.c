@@ -160,7 +160,54 @@ __attribute__((constructor)) static void early_device_start (int argc, char** ar
 	if (files >= 2) lzgpu_init_async (-1);
 	}
 
-static void drop_device_table (void) { devTable = NULL;  devTargetV = NULL;  devTargetLen = 0;  devTableOnHost = false;  devLimit = 0; }
+/* ---- dynamic masking (--masking=<count>) on the device, under LZGPU_MASKING=1 only: the default stays the reference's routine.
+ * mask_interval (src/masking.c:303-358) reports every interval to mask_seed_position_table BEFORE it writes the 'x' bytes,
+ * and all intervals of a (query, strand) arrive between two uses of the table.  The hook queues them; flush_masks(), at the
+ * top of everything that uses the device's table or target, copies the bytes -- 'x' by then -- and takes the entries out
+ * of the device's table in one lzgpu_table_mask call. */
+static lz_interval* devMasks = NULL;   static u32 devMasksLen = 0, devMasksCap = 0;
+static int          devTableFiltered = false;               /* a --self or --chores search has used this table: its masking keeps the reference's path */
+
+static int masking_on_device (void)
+	{
+	static int v = -1;
+	if (v < 0) { char* e = getenv ("LZGPU_MASKING");  v = ((e != NULL) && (e[0] == '1') && (e[1] == 0)); }
+	return v;
+	}
+
+static void drop_device_table (void)
+	{ devTable = NULL;  devTargetV = NULL;  devTargetLen = 0;  devTableOnHost = false;  devLimit = 0;  devMasksLen = 0;  devTableFiltered = false; }
+
+#define devMaskGap 65536u
+static int by_start (const void* a, const void* b)
+	{
+	uint32_t x = ((const lz_interval*) a)->start, y = ((const lz_interval*) b)->start;
+	return (x < y)? -1 : (x > y)? 1 : 0;
+	}
+
+static void flush_masks (void)
+	{
+	u32 k;
+	int rc;
+	if (devMasksLen == 0) return;
+	/* the widened interval is a superset of the bytes that changed; eligibility was checked when the intervals were queued,
+	   and the bytes the reference's routine would read are gone: anything but success is fatal */
+	rc = lzgpu_table_mask (devMasks, devMasksLen);              /* (the intervals as the reference reported them: merging two changes what goes) */
+	if (rc != 0) suicidef ("lzgpu_table_mask: %s (%d)", lzgpu_last_error(), rc);
+	/* the bytes: a copy costs the same few microseconds whatever its length, so intervals that overlap, abut or lie within
+	   devMaskGap bytes of each other go in one (the bytes between them are copied unchanged) */
+	qsort (devMasks, devMasksLen, sizeof(lz_interval), by_start);
+	for (k=0 ; k<devMasksLen ; )
+		{
+		uint32_t s = devMasks[k].start, e = devMasks[k].end;
+		for (k++ ; (k<devMasksLen) && (devMasks[k].start <= e + devMaskGap) ; k++)
+			if (devMasks[k].end > e) e = devMasks[k].end;
+		rc = lzgpu_target_update (s, devTargetV + s, e - s);
+		if (rc != 0) suicidef ("lzgpu_target_update: %s (%d)", lzgpu_last_error(), rc);
+		}
+	devMasksLen = 0;
+	note ("mask", "done on the GPU");
+	}
 
 /* The host copy in the reference's layout (last[] / prev[]) costs a device-to-host copy of 64 MiB + 4 bytes per
  * target base; the search and the gapped stage never read it.  It is made on demand: before any reference routine
@@ -168,6 +215,7 @@ static void drop_device_table (void) { devTable = NULL;  devTargetV = NULL;  dev
 static void host_table_needed (postable* pt)
 	{
 	int rc;
+	flush_masks ();
 	if ((pt == NULL) || (pt != devTable) || (devTableOnHost)) return;
 	rc = lzgpu_table_export (pt->last, pt->prev);
 	if (rc != 0) suicidef ("lzgpu_table_export: %s", lzgpu_last_error());
@@ -476,9 +524,29 @@ void free_position_table (postable* pt)
 void mask_seed_position_table
    (postable* pt, seq* seq, unspos start, unspos end, const s8 upperCharToBits[], seed* hitSeed)
 	{
-	/* dynamic masking (--masking=<count>, src/masking.c) has just rewritten bases of seq->v IN PLACE and now
-	   removes their seeds from the table: the device's table AND its copy of the target bytes (which the gapped
-	   stage reads, with or without a table) are stale from here on */
+	/* dynamic masking (--masking=<count>, src/masking.c) removes the seeds of an interval from the table and then rewrites
+	   its bases in seq->v IN PLACE: the device's table AND its copy of the target bytes (which the gapped stage reads, with
+	   or without a table) are stale from here on -- unless the interval is queued for the device (LZGPU_MASKING=1) */
+	if (masking_on_device ())
+		{
+		multi_init ();
+		if ((pt != NULL) && (pt == devTable) && (seq != NULL) && (seq->v == devTargetV) && (devLimit == 0) && (mgWorld == 1)
+		 && (!devTableFiltered))
+			{
+			/* (the reference's sanity checks, src/pos_table.c:757-766) */
+			if (end == 0) end = seq->len;
+			if (end <= start)
+				suicidef ("in mask_seed_position_table(), interval is void (" unsposFmt "-" unsposFmt ")", start, end);
+			if (end > seq->len)
+				suicidef ("in mask_seed_position_table(), interval end is bad (" unsposFmt ">" unsposFmt ")", end, seq->len);
+			if (devMasksLen == devMasksCap)
+				{ devMasksCap = 2*devMasksCap + 64;  devMasks = (lz_interval*) realloc_or_die ("lzgpu masked intervals", devMasks, devMasksCap * sizeof(lz_interval)); }
+			devMasks[devMasksLen].start = (uint32_t) start;  devMasks[devMasksLen].end = (uint32_t) end;  devMasksLen++;
+			if (devTableOnHost) ref_mask_seed_position_table (pt, seq, start, end, upperCharToBits, hitSeed);   /* (the host copy stays in step) */
+			return;
+			}
+		note ("mask", "reference path");
+		}
 	host_table_needed (pt);
 	if ((pt == devTable) || ((seq != NULL) && (seq->v == devTargetV))) drop_device_table ();
 	ref_mask_seed_position_table (pt, seq, start, end, upperCharToBits, hitSeed);
@@ -533,7 +601,7 @@ u32 find_position_table_limit (postable* pt, float keep)
 	}
 
 u64 write_capsule_file (FILE* f, char* filename, seq* seq, u8* revNucs, postable* pt, seed* seed)
-	{ host_table_needed (pt);  return ref_write_capsule_file (f, filename, seq, revNucs, pt, seed); }
+	{ flush_masks ();  host_table_needed (pt);  return ref_write_capsule_file (f, filename, seq, revNucs, pt, seed); }
 
 u32 quantum_seed_hit_search
    (seq* seq1, postable* pt, seq* seq2, unspos start, unspos end, const s8 charToBits[], seed* hitSeed,
@@ -583,6 +651,8 @@ u64 seed_hit_search
 		}
 
 	clock_mark ("search", "called");
+	flush_masks ();
+	if ((pt == devTable) && ((selfCompare) || (hp->posFilter))) devTableFiltered = true;
 	/* --mismatch=<count>,<length> goes to the device only under LZGPU_MISMATCH=1: the default stays the reference's routine */
 	mismatchExtend = (processor == process_for_simple_hit) && (hp->gfExtend >= gfexMismatch_min) && (hp->gfExtend <= gfexMismatch_max)
 	              && ((mmEnv = getenv ("LZGPU_MISMATCH")) != NULL) && (mmEnv[0] == '1') && (mmEnv[1] == 0);
@@ -713,7 +783,7 @@ alignel* gapped_extend
 	alignel*       head = NULL, *last = NULL, *el;
 	int            rc;
 
-	if (twMode == twOff) clock_mark ("gapped", "called");
+	if (twMode == twOff) { clock_mark ("gapped", "called");  flush_masks (); }
 	if (twMode == twReplaySearch)                               /* a window's anchors (chained by the reference): noted, extended later */
 		{
 		twWindow* w = &twWin[twCursor-1];
@@ -912,6 +982,7 @@ alignel* tweener_interpolate
 	int          rc;
 	alignel*     res;
 
+	flush_masks ();
 	if ((alignList == NULL) || (getenv ("LZGPU_NO_WINDOW_BATCH") != NULL)
 	 || (devTargetV == NULL) || (seq1->v != devTargetV) || (seq1->len != devTargetLen)
 	 || (seq1->partition.p != NULL) || (seq2->partition.p != NULL) || (seq2->fileType == seq_type_qdna)

@@ -77,7 +77,7 @@ struct LzCtx {
     LzSeedDev seed;
     DevBuf wstart, wpos;            // CSR table
     u64 num_words = 0;
-    u64 table_gen = 0;              // counts the changes of wpos (table build, adopt, commit, a word-count limit set or lifted)
+    u64 table_gen = 0;              // counts the changes of wpos (table build, adopt, commit, a word-count limit set or lifted, a masking pass that removed entries)
     // a word-count limit in force (lzgpu_table_limit, limit_kernels.hip): wstart / wpos / num_words above are the LIMITED table the
     // searches read, and the table as it was built stands aside here; without a limit these are empty
     u32 limit = 0;                  // 0: none
@@ -126,7 +126,8 @@ struct LzCtx {
     DevBuf hsp_out, hsp_count;      // candidates + counter
     DevBuf hsp_mc;                  // [n][5]: A/C/G/T match counts of the candidates (entropy inputs) + probe index
     DevBuf dev_counters;            // u64[8]
-    DevBuf tb_keys, tb_vals, tb_keys2, tb_vals2;   // table build scratch
+    DevBuf tb_keys, tb_vals, tb_keys2, tb_vals2;   // table build scratch; a masking pass (mask_kernels.hip) borrows tb_keys, tb_keys2 and tb_vals2
+    DevBuf mask_bits, mask_ranges;  // dynamic masking: one bit per target position 0 .. tlen, and the removal ranges of one lzgpu_table_mask call
     // ---- gapped stage (B3) and window search: device memory and settings that used to live at file scope
     // Threading: `dp` is touched on dp_stream only, by lzgpu_gapped_extend_batch's caller before its workers start and then by whichever
     // worker holds the batch rendezvous (HipDpExec::run_multi: one at a time); the win_* buffers on `stream` only, by lzgpu_window_search's caller.
@@ -166,7 +167,7 @@ struct LzCtx {
     {
         DevBuf* all[] = { &wstart, &wpos, &full_wstart, &full_wpos, &wctx, &cnt, &off, &pk, &wiv, &wsk, &wsv, &blk_start, &bins, &keys, &keys2, &filter_keep, &filter_counts, &filter_bases, &bin_base, &hist, &hist_part, &run_addr,
                           &summ, &scan_tasks, &scan_ntasks, &lut, &sort_tmp, &scan_tmp, &diag_end, &score_tab, &cls_t, &cls_q, &cls_tmp, &win_tab, &match_tmp,
-                          &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &self_sep,
+                          &hsp_out, &hsp_count, &hsp_mc, &dev_counters, &tb_keys, &tb_vals, &tb_keys2, &tb_vals2, &mask_bits, &mask_ranges, &self_sep,
                           &dp.jobs, &dp.ids, &dp.res, &dp.tab, &dp.tb, &dp.rows, &dp.ops, &dp.ops_off, &dp.ops_out, &dp.pieces, &dp.rings, &dp.sel_jobs, &dp.sel_res, &dp.problems,
                           &win_jobs, &win_scratch, &win_out, &win_count };
         for (DevBuf* b : all) b->release();
@@ -204,6 +205,8 @@ int lzk_wctx_build(LzCtx& c);       // c.wctx (allocated by the caller) from c.w
 void lz_limit_lift(LzCtx& c);       // c.wstart / c.wpos / c.num_words are the table as it was built again; the limited copy is released
 int lzk_table_limit(LzCtx& c, u32 limit);                        // c.wstart / c.wpos -> the copy without the words of more than `limit` entries, put in their place
 int lzk_table_count_distribution(LzCtx& c, std::vector<u32>& count, std::vector<u32>& words);   // the distinct list lengths > 0, ascending, and the words that have each
+// mask_kernels.hip (synchronises c.stream)
+int lzk_table_mask(LzCtx& c, const lz_interval* iv, u32 n, u32 tlen);   // c.wstart / c.wpos without the entries p, iv[k].start + L <= p <= iv[k].end; c.num_words, c.geom.num_words and c.table_gen follow when something went
 // enum_kernels.hip (the query positions [lo, hi), n = hi - lo of them: c.cnt, c.off, c.pk, c.wiv, c.wsk, c.wsv, sized by the caller)
 int lzk_count_hits(LzCtx& c, const u8* qcode, u32 lo, u32 hi);   // honours c.n_owners / c.owner and c.self
 int lzk_scan_counts(LzCtx& c, u32 n);

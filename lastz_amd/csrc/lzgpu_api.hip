@@ -407,6 +407,41 @@ extern "C" int lzgpu_target_patch(const uint32_t* pos, const uint8_t* bytes, uin
     return 0;
 }
 
+// The range form of lzgpu_target_patch: len bytes from `start` on, in one copy (the bases dynamic masking turns into 'x').
+extern "C" int lzgpu_target_update(uint32_t start, const uint8_t* bytes, uint32_t len)
+{
+    int rc = require_init(); if (rc) return rc;
+    LzCtx& c = g_ctx;
+    if (len && !bytes) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    if (!c.target.have_raw || c.target.host.size() != c.target.len) return lz_fail(LZGPU_ERR_STATE, "no target on the device");
+    if (start > c.target.len || len > c.target.len - start) return lz_fail(LZGPU_ERR_ARG, "target range %u+%u is past the end (%u)", start, len, c.target.len);
+    if (!len) return 0;
+    memcpy(&c.target.host[start], bytes, len);
+    LZ_HIP(hipMemcpyAsync(c.target.raw_base() + start, &c.target.host[start], len, hipMemcpyHostToDevice, c.stream));
+    LZ_HIP(hipStreamSynchronize(c.stream));
+    c.target.code_key = 0; c.target.dp_key = 0; c.target.match_key = 0;
+    c.wctx_gen = 0; c.wctx_code_key = 0;
+    return 0;
+}
+
+// ---- dynamic masking (lastz --masking=<count>)
+// mask_seed_position_table (src/pos_table.c:747-887; called through mask_interval's callback, src/lastz.c:3787-3806) for n
+// intervals at once, on the resident table in place (mask_kernels.hip).
+extern "C" int lzgpu_table_mask(const lz_interval* iv, uint32_t n)
+{
+    LzCtx& c = g_ctx;
+    if (!c.have_table) return lz_fail(LZGPU_ERR_STATE, "no position table");
+    if (n && !iv) return lz_fail(LZGPU_ERR_ARG, "null argument");
+    for (u32 k = 0; k < n; k++) {
+        if (iv[k].end <= iv[k].start) return lz_fail(LZGPU_ERR_ARG, "interval is void (%u..%u)", iv[k].start, iv[k].end);
+        if (iv[k].end > c.geom.tlen)  return lz_fail(LZGPU_ERR_ARG, "interval end is bad (%u>%u)", iv[k].end, c.geom.tlen);
+    }
+    if (c.limit != 0 || c.n_owners > 1) return LZGPU_NH_UNSUPPORTED;
+    if (!n) return 0;
+    int rc = lz_bind_thread(); if (rc) return rc;
+    return lzk_table_mask(c, iv, n, c.geom.tlen);
+}
+
 extern "C" int lzgpu_table_rebuild(void)
 {
     LzCtx& c = g_ctx;

@@ -78,7 +78,7 @@ ALIGN_DTYPE = np.dtype([("beg1", "<u4"), ("beg2", "<u4"), ("end1", "<u4"), ("end
 
 # every symbol include/lzgpu.h declares (tests check that the library exports all of them)
 EXPORTS = ["lzgpu_seed_from_pattern", "lzgpu_probe", "lzgpu_init", "lzgpu_device_index", "lzgpu_init_async", "lzgpu_shutdown", "lzgpu_free",
-           "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_table_num_words",
+           "lzgpu_last_error", "lzgpu_table_prepare", "lzgpu_table_export", "lzgpu_table_rebuild", "lzgpu_target_patch", "lzgpu_target_update", "lzgpu_table_mask", "lzgpu_table_num_words",
            "lzgpu_table_geom", "lzgpu_table_adopt", "lzgpu_table_buffers", "lzgpu_table_commit", "lzgpu_table_share", "lzgpu_table_save", "lzgpu_table_load", "lzgpu_table_limit", "lzgpu_table_find_limit", "lzgpu_table_count_distribution", "lzgpu_device_copy",
            "lzgpu_seed_hit_search", "lzgpu_seed_hit_search_self", "lzgpu_seed_hit_search_within", "lzgpu_seed_hit_search_exact", "lzgpu_seed_hit_search_mismatch", "lzgpu_query_upload", "lzgpu_target_upload", "lzgpu_gapped_extend", "lzgpu_gapped_extend_batch", "lzgpu_window_search",
            "lzgpu_counters_reset", "lzgpu_counters_get", "lzgpu_profile_enable", "lzgpu_profile_reset",
@@ -133,6 +133,8 @@ class Lib:
             self.L.lzgpu_device_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
             self.L.lzgpu_query_upload.argtypes = [C.c_int32, C.c_void_p, C.c_uint32]
             self.L.lzgpu_target_upload.argtypes = [C.c_void_p, C.c_uint32]
+            self.L.lzgpu_target_update.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32]
+            self.L.lzgpu_table_mask.argtypes = [C.c_void_p, C.c_uint32]
             self.L.lzgpu_gapped_extend_batch.argtypes = [C.POINTER(GappedArgs), C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                                          C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
             self.L.lzgpu_gapped_extend.argtypes = [C.POINTER(GappedArgs), C.POINTER(C.c_void_p),
@@ -191,6 +193,18 @@ class Lib:
         assert len(pos) == len(values)
         self.L.lzgpu_target_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         self._check(self.L.lzgpu_target_patch(_ptr(pos), _ptr(values), len(pos)), "lzgpu_target_patch")
+
+    def target_update(self, start, values):
+        """t[start : start + len(values)] = values in the resident target, in one copy (the bases lastz --masking turns
+        into 'x'); the table stays as it is"""
+        values = np.ascontiguousarray(values, dtype=np.uint8)
+        self._check(self.L.lzgpu_target_update(start, _ptr(values), len(values)), "lzgpu_target_update")
+
+    def table_mask(self, intervals):
+        """lastz --masking: mask_seed_position_table for every (start, end) of `intervals` (origin 0, end-exclusive, already
+        widened by L - 1): the entries p with start + L <= p <= end leave the resident table, everything else keeps its place"""
+        iv = np.ascontiguousarray(np.array(intervals, dtype=np.uint32).reshape(-1, 2))
+        self._check(self.L.lzgpu_table_mask(_ptr(iv), len(iv)), "lzgpu_table_mask")
 
     def table_rebuild(self):
         self._check(self.L.lzgpu_table_rebuild(), "lzgpu_table_rebuild")
