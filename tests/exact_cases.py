@@ -217,16 +217,22 @@ def emul():
     return _once("emul", make)
 
 
+def run_on(fn, v, q, p1, p2, L, thr, n_extra):
+    """one of the two routines over any sequences and any hit list in discovery order (a seed of length L, threshold thr):
+    (HSPs in discovery order, the routine's extra words)"""
+    p1, p2 = np.ascontiguousarray(p1, dtype=np.uint32), np.ascontiguousarray(p2, dtype=np.uint32)
+    rows = np.zeros(4 * max(len(p1), 1), dtype=np.uint32)
+    n, extra = np.zeros(1, dtype=np.uint64), np.zeros(n_extra, dtype=np.uint64)
+    rc = fn(np.ascontiguousarray(v), len(v), np.ascontiguousarray(q), len(q), match_bits(), L, thr, p1, p2, len(p1), rows, n, extra)
+    assert rc == 0
+    return rows[:4 * int(n[0])].reshape(-1, 4).copy().view(HSP_DTYPE).reshape(-1), extra
+
+
 def _run(fn, lzo, name, n_extra):
     c = CASES[name]
     v, _, q = sequences(name)
     p1, p2, _ = raw_hits(lzo, name)
-    rows = np.zeros(4 * max(len(p1), 1), dtype=np.uint32)
-    n, extra = np.zeros(1, dtype=np.uint64), np.zeros(n_extra, dtype=np.uint64)
-    L = len(c["pattern"])
-    rc = fn(np.ascontiguousarray(v), len(v), np.ascontiguousarray(q), len(q), match_bits(), L, c["thr"], p1, p2, len(p1), rows, n, extra)
-    assert rc == 0
-    return rows[:4 * int(n[0])].reshape(-1, 4).copy().view(HSP_DTYPE).reshape(-1), extra
+    return run_on(fn, v, q, p1, p2, len(c["pattern"]), c["thr"], n_extra)
 
 
 def serial(lzo, name):

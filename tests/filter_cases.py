@@ -102,9 +102,14 @@ def scoring(name):
     return EC._once(("fscoring", "--ambiguous=iupac" in CASES[name]["extra"]), make)
 
 
+def case_of(name):
+    """a case of CASES by its name, or a dict with the fields the predicates read (pattern, cares, M, T) as it is"""
+    return CASES[name] if isinstance(name, str) else name
+
+
 def positions(name):
     """lz_hit_filter.positions of the case"""
-    c = CASES[name]
+    c = case_of(name)
     L = len(c["pattern"])
     if not c["cares"]:
         return (1 << L) - 1
@@ -229,7 +234,7 @@ def _T(c):
 def by_bytes(name, t, q, p1, p2):
     """filter_seed_hit_by_subs over the windows ending at (p1, p2): (verdict per hit: 0 kept, 1 few matches, 2 many transversions;
     (matches, transversions) per hit)"""
-    c = CASES[name]
+    c = case_of(name)
     p1, p2 = np.ascontiguousarray(p1, dtype=np.uint32), np.ascontiguousarray(p2, dtype=np.uint32)
     verdict, counts = np.zeros(max(len(p1), 1), dtype=np.uint8), np.zeros(2 * max(len(p1), 1), dtype=np.uint8)
     rc = emul().emul_filter_bytes(np.ascontiguousarray(t), np.ascontiguousarray(q), match_bits(), len(c["pattern"]), positions(name),
@@ -240,7 +245,7 @@ def by_bytes(name, t, q, p1, p2):
 
 def by_codes(name, t, q, p1, p2):
     """lz_filter.hpp's predicate on match codes: (keeps per hit: 1 / 0; (matches, transversions) per hit)"""
-    c = CASES[name]
+    c = case_of(name)
     p1, p2 = np.ascontiguousarray(p1, dtype=np.uint32), np.ascontiguousarray(p2, dtype=np.uint32)
     keeps, counts = np.zeros(max(len(p1), 1), dtype=np.uint8), np.zeros(2 * max(len(p1), 1), dtype=np.uint8)
     rc = emul().emul_filter_codes(np.ascontiguousarray(t), len(t), np.ascontiguousarray(q), len(q), match_bits(), len(c["pattern"]),
@@ -265,38 +270,41 @@ def expected(lzo, name, strand="+"):
     """the case's search as the reference runs it: dict(hsps in the reporter's order, raw, dropped, and where the search
     counts them extensions, bp_extended)"""
     def make():
-        import helpers as H
-        c = CASES[name]
-        v, _, _ = sequences(name)
-        q = query_of(name, strand)
         p1, p2, st = raw_hits(lzo, name, strand)
-        keep = verdicts(lzo, name, strand)[0] == 0
-        k1, k2 = np.ascontiguousarray(p1[keep]), np.ascontiguousarray(p2[keep])
-        out = dict(raw=len(p1), dropped=int(len(p1) - keep.sum()), words=st["words"])
-        L = len(c["pattern"])
-        rows, n = np.zeros(4 * max(len(k1), 1), dtype=np.uint32), np.zeros(1, dtype=np.uint64)
-        vv, qq = np.ascontiguousarray(v), np.ascontiguousarray(q)
-        if c["kind"] == "plain":
-            hs = np.zeros(len(k1), dtype=EC.HSP_DTYPE)
-            hs["pos1"], hs["pos2"], hs["length"] = k1, k2, L
-            out.update(hsps=hs)
-        elif c["kind"] == "exact":
-            rc = EC.emul().emul_exact_serial(vv, len(vv), qq, len(qq), match_bits(), L, c["thr"], k1, k2, len(k1), rows, n, np.zeros(5, dtype=np.uint64))
-            assert rc == 0
-            out.update(hsps=_rows(rows, n[0]), extensions=0, bp_extended=0)
-        elif c["kind"] == "mismatch":
-            rc = MC.emul().emul_mismatch_serial(vv, len(vv), qq, len(qq), match_bits(), L, c["mm"], c["thr"], k1, k2, len(k1), rows, n,
-                                                np.zeros(len(MC.COUNTERS), dtype=np.uint64), np.zeros(MC.DIAG_SIZE, dtype=np.uint32))
-            assert rc == 0
-            out.update(hsps=_rows(rows, n[0]), extensions=0, bp_extended=0)
-        else:
-            cn = np.zeros(2, dtype=np.uint64)
-            rc = emul().emul_filter_xdrop(vv, len(vv), qq, len(qq), table_bits(lzo, name), scoring(name), 910, 3000, 1,
-                                          c["pattern"].encode(), c["trans"], k1, k2, len(k1), rows, n, cn)
-            assert rc == 0
-            out.update(hsps=_rows(rows, n[0]), extensions=int(cn[0]), bp_extended=int(cn[1]))
-        return out
+        return search_over(CASES[name], sequences(name)[0], query_of(name, strand), p1, p2, verdicts(lzo, name, strand)[0] == 0,
+                           st["words"], table_bits(lzo, name), scoring(name))
     return EC._once(("fexpected", name, strand), make)
+
+
+def search_over(c, v, q, p1, p2, keep, words, ctb, masked):
+    """the statement over any sequences and any raw hits in discovery order: the search of kind c["kind"] (with c's pattern,
+    trans, thr, mm) over the hits `keep` marks -> dict(hsps, raw, dropped, words and, where the search counts them, extensions,
+    bp_extended); ctb, masked: the table's char_to_bits and the masked matrix of an X-drop search"""
+    k1, k2 = np.ascontiguousarray(p1[keep], dtype=np.uint32), np.ascontiguousarray(p2[keep], dtype=np.uint32)
+    out = dict(raw=len(p1), dropped=int(len(p1) - keep.sum()), words=words)
+    L = len(c["pattern"])
+    rows, n = np.zeros(4 * max(len(k1), 1), dtype=np.uint32), np.zeros(1, dtype=np.uint64)
+    vv, qq = np.ascontiguousarray(v), np.ascontiguousarray(q)
+    if c["kind"] == "plain":
+        hs = np.zeros(len(k1), dtype=EC.HSP_DTYPE)
+        hs["pos1"], hs["pos2"], hs["length"] = k1, k2, L
+        out.update(hsps=hs)
+    elif c["kind"] == "exact":
+        rc = EC.emul().emul_exact_serial(vv, len(vv), qq, len(qq), match_bits(), L, c["thr"], k1, k2, len(k1), rows, n, np.zeros(5, dtype=np.uint64))
+        assert rc == 0
+        out.update(hsps=_rows(rows, n[0]), extensions=0, bp_extended=0)
+    elif c["kind"] == "mismatch":
+        rc = MC.emul().emul_mismatch_serial(vv, len(vv), qq, len(qq), match_bits(), L, c["mm"], c["thr"], k1, k2, len(k1), rows, n,
+                                            np.zeros(len(MC.COUNTERS), dtype=np.uint64), np.zeros(MC.DIAG_SIZE, dtype=np.uint32))
+        assert rc == 0
+        out.update(hsps=_rows(rows, n[0]), extensions=0, bp_extended=0)
+    else:
+        cn = np.zeros(2, dtype=np.uint64)
+        rc = emul().emul_filter_xdrop(vv, len(vv), qq, len(qq), ctb, np.ascontiguousarray(masked), 910, 3000, 1,
+                                      c["pattern"].encode(), c["trans"], k1, k2, len(k1), rows, n, cn)
+        assert rc == 0
+        out.update(hsps=_rows(rows, n[0]), extensions=int(cn[0]), bp_extended=int(cn[1]))
+    return out
 
 
 def reach(lzo, name):
@@ -340,9 +348,12 @@ parse_rows = EC.parse_rows
 def sweep(name, n=400, seed=7):
     """window ends for the predicates beyond the raw hits: at both ends of both sequences (pos = L and pos = len), at random, on
     the main diagonal and -- a [multi] target -- across every NUL; (pos1, pos2)"""
-    c = CASES[name]
     v, seps, q = sequences(name)
-    L = len(c["pattern"])
+    return sweep_over(v, seps, q, len(CASES[name]["pattern"]), n, seed)
+
+
+def sweep_over(v, seps, q, L, n=400, seed=7):
+    """sweep() over any sequences and any window length"""
     rng = np.random.default_rng(seed)
     ends1 = [L, L + 1, len(v) - 1, len(v)] + [s + d for s in seps for d in range(1, L + 2) if L <= s + d <= len(v)]
     ends2 = [L, L + 1, len(q) - 1, len(q)]

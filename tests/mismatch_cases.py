@@ -146,16 +146,22 @@ def emul():
     return EC._once("emul_mismatch", make)
 
 
+def run_on(fn, v, q, p1, p2, L, M, thr, extra):
+    """one of the two routines over any sequences and any hit list in discovery order (a seed of length L, M mismatches,
+    threshold thr): (HSPs in discovery order, diagEnd as the routine leaves it); extra: its counters[] or form[]"""
+    p1, p2 = np.ascontiguousarray(p1, dtype=np.uint32), np.ascontiguousarray(p2, dtype=np.uint32)
+    rows = np.zeros(4 * max(len(p1), 1), dtype=np.uint32)
+    n, dend = np.zeros(1, dtype=np.uint64), np.zeros(DIAG_SIZE, dtype=np.uint32)
+    rc = fn(np.ascontiguousarray(v), len(v), np.ascontiguousarray(q), len(q), match_bits(), L, M, thr, p1, p2, len(p1), rows, n, extra, dend)
+    assert rc == 0, rc
+    return rows[:4 * int(n[0])].reshape(-1, 4).copy().view(EC.HSP_DTYPE).reshape(-1), dend
+
+
 def _run(fn, lzo, name, extra, interval=(0, 0)):
     c = CASES[name]
     v, _, q = sequences(name)
     p1, p2, _ = raw_hits(lzo, name, interval)
-    rows = np.zeros(4 * max(len(p1), 1), dtype=np.uint32)
-    n, dend = np.zeros(1, dtype=np.uint64), np.zeros(DIAG_SIZE, dtype=np.uint32)
-    rc = fn(np.ascontiguousarray(v), len(v), np.ascontiguousarray(q), len(q), match_bits(), len(c["pattern"]), c["M"], c["thr"],
-            p1, p2, len(p1), rows, n, extra, dend)
-    assert rc == 0, rc
-    return rows[:4 * int(n[0])].reshape(-1, 4).copy().view(EC.HSP_DTYPE).reshape(-1), dend
+    return run_on(fn, v, q, p1, p2, len(c["pattern"]), c["M"], c["thr"], extra)
 
 
 def serial(lzo, name, interval=(0, 0)):
